@@ -19,12 +19,18 @@ candidates] -> cross-shard merge (K4).  One process per GPU.
                    MedRAG's 4 corpora, k = 32; synthetic embeddings, tools/workloads.py) placed on the N GPUs by
                    ragroute_amd/placement.py: balanced row slices, the pieces of one encoder on a rank searched in one pass.
                    Fixed federation = strong scaling; `value` = queries/sec against the whole federation.
-Every N > 1 line carries `per_rank_scan_ms` / `per_rank_local_ms` (each rank's scan-launch time and its whole local work per step,
-one small all_gather after the timed region): a slow rank is visible.
-Every line also carries `exchange_ms` / `merge_ms` (HIP events around the all_gather and the merge, mean per step on rank 0)
-and `rccl_ranks` (dist.get_world_size() after init_process_group; 1 without a process group).
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, the configuration) and
+nothing else.  `--full` adds everything measured beside it, as separate passes after the timed steps:
+  * one HIP-event pair per timed step (`median_ms` / `p10_ms` / `p90_ms`) and the live scan-launch times behind `roofline`;
+  * `per_rank_scan_ms` / `per_rank_local_ms` (each rank's scan-launch time and its whole local work per step, one small
+    all_gather after the timed region): a slow rank is visible;
+  * `exchange_ms` / `merge_ms` (HIP events around the all_gather and the merge, mean per step on rank 0) and `result_checksum`;
+  * the sustained block (`--sustained-seconds`) and, at N = 1 on the headline workload, the CPU baseline (`--no-cpu-baseline`).
+Every line carries `rccl_ranks` (dist.get_world_size() after init_process_group; 1 without a process group).
+`--dump-outputs DIR` writes what the timed path returned in its last step (scores and ids, see dump_outputs) as DIR/*.npy; the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 `python bench.py --gpus N` without a launcher starts the N ranks itself as child processes (the parent never touches the GPU).
@@ -44,9 +50,10 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0       # MI355X HBM3E spec (MI355X_MICROARCH.md, chip-level parameters)
 MFMA_PEAK_TFLOPS = 2500.0   # dense fp16/bf16
 METRIC = "queries/sec route+top-k, d=768 fp16, 10M docs/shard, k=32; top-k recall vs CPU"
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
@@ -62,10 +69,18 @@ def parse_args():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--k", type=int, default=None, help="default: 32 (headline), the dataset's K (config.py:97-101) for --workload")
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: per-step events, roofline, per-rank times, "
+                         "checksums, the sustained block and the CPU baseline (a plain run does none of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the scores and ids the timed path returned in its last step as DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
     ap.add_argument("--sustained-seconds", type=float, default=2.0,
-                    help="extra steady-state block after the timed steps (>= this long and >= 500 batches); 0 disables it")
-    return ap.parse_args()
+                    help="--full: extra steady-state block after the timed steps (>= this long and >= 500 batches); 0 disables it")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launch_ranks(args):
@@ -116,6 +131,31 @@ def percentile(sorted_vals, p):
     lo = int(i)
     hi = min(lo + 1, len(sorted_vals) - 1)
     return sorted_vals[lo] + (sorted_vals[hi] - sorted_vals[lo]) * (i - lo)
+
+
+def dump_outputs(out_dir, D, I, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what a caller of the timed path receives, (D f32 [B, k], I i64 [B, k]), as out_dir/scores.npy (float32)
+    and out_dir/ids.npy (float64: every id, shard << 40 | row or -1, is exact below 2^53).  Padding slots (id -1, score -inf
+    as FAISS pads; a query the router sends nowhere is all padding) are written with score 0, so every value in the files is
+    finite and ids == -1 still marks them; their scores sum to result_checksum's score_sum.  If the two would exceed `limit`
+    bytes, a fixed sample of query rows (numpy seed 0) is written instead, its row numbers in out_dir/query_rows.npy."""
+    import numpy as np
+    D = D.detach().float().cpu().numpy().copy()
+    I = I.detach().cpu().numpy()
+    D[(I == -1) & ~np.isfinite(D)] = 0.0
+    assert D.shape == I.shape and (I.size == 0 or int(np.abs(I).max()) < 1 << 53), "ids not exact in float64"
+    rows = None
+    per_row = D.shape[1] * (4 + 8) + 8
+    if D.shape[0] * per_row > limit:
+        rows = np.sort(np.random.default_rng(0).choice(D.shape[0], max(1, limit // per_row), replace=False))
+        D, I = D[rows], I[rows]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "scores.npy"), np.ascontiguousarray(D, dtype=np.float32))
+    np.save(os.path.join(out_dir, "ids.npy"), np.ascontiguousarray(I, dtype=np.float64))
+    if rows is not None:
+        np.save(os.path.join(out_dir, "query_rows.npy"), rows.astype(np.float64))
+    elif os.path.exists(os.path.join(out_dir, "query_rows.npy")):
+        os.remove(os.path.join(out_dir, "query_rows.npy"))   # left by an earlier, sampled dump
 
 
 def main():
@@ -230,35 +270,88 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    def timed(n_steps, with_events):
-        """n_steps back-to-back steps: wall clock between two fences (max over ranks), live HIP-event time of every scan
-        launch (rr_profile_*), and optionally one HIP-event pair per step on the launch stream."""
+    def timed(n_steps, with_events, profile=True):
+        """n_steps back-to-back steps: wall clock between two fences (max over ranks), optionally the live HIP-event time of
+        every scan launch (rr_profile_*) and one HIP-event pair per step on the launch stream.  Also returns the last step's
+        (D, I)."""
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_steps)] if with_events else []
         fence()
         # scan launches per shard and step: bootstrap + up to 8 chunks (capi.hip chunk_schedule), per 256-query block;
         # rr_profile_end FAILS if a launch went unrecorded, so the roofline cannot be overstated by a short buffer
-        check(lib().rr_profile_begin(n_steps * 12 * n_units * (-(-B // 256)) + 16), "rr_profile_begin")
+        if profile:
+            check(lib().rr_profile_begin(n_steps * 12 * n_units * (-(-B // 256)) + 16), "rr_profile_begin")
+        out = None
         t0 = time.perf_counter()
         for i in range(n_steps):
             if with_events:
                 evs[i][0].record()
-            step()
+            out = step()
             if with_events:
                 evs[i][1].record()
         fence()
         elapsed = time.perf_counter() - t0
         scan_ms, n_launch, rows_scanned = ctypes.c_double(), ctypes.c_int(), ctypes.c_double()
-        check(lib().rr_profile_end(ctypes.byref(scan_ms), ctypes.byref(n_launch), ctypes.byref(rows_scanned)), "rr_profile_end")
+        if profile:
+            check(lib().rr_profile_end(ctypes.byref(scan_ms), ctypes.byref(n_launch), ctypes.byref(rows_scanned)), "rr_profile_end")
         if world > 1:
             t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
         per_step = sorted(a.elapsed_time(b) for a, b in evs)
-        return elapsed, scan_ms.value, n_launch.value, per_step
+        return elapsed, scan_ms.value, n_launch.value, per_step, out
 
     for _ in range(args.warmup):
         step()
-    elapsed, scan_ms, n_launch, per_step = timed(args.steps, True)
+    # a plain run times the bare steps; --full adds the per-step event pairs and the per-launch scan events of the roofline
+    elapsed, scan_ms, n_launch, per_step, (D_last, I_last) = timed(args.steps, args.full, profile=args.full)
+    # every rank holds the same merged answer; a device copy (no host read) keeps it for the dump at the end of the run
+    last = (D_last.clone(), I_last.clone()) if args.dump_outputs and rank == 0 else None
+    del D_last, I_last
+    rccl_ranks = dist.get_world_size() if (world > 1 and dist.is_initialized()) else 1
+    K = args.steps
+    units = B if strong else world * B                 # queries per step the whole job answers (weak: query x shard)
+    if fed_mode:
+        total_rows = sum(s_.rows for s_ in fed)
+        total_gb = sum(s_.rows * s_.row_bytes for s_ in fed) / 1e9
+        config = {"workload": f"{args.workload}: {C} sources at {'their real row counts' if args.workload_scale == 1 else f'1/{args.workload_scale} of their real row counts'} and encoder widths ({total_rows} rows, {total_gb:.1f} GB fp16), "
+                              f"{'balanced row slices (placement.plan)' if args.placement == 'sliced' else 'source s -> GPU s mod G'} over {world} GPU(s), "
+                              f"query batch {B}, k={k}, router MLP + per-unit exact top-k + ONE all_gather + merge",
+                  "dataset": args.workload, "row_scale": f"1/{args.workload_scale}", "placement": args.placement, "rows_total": total_rows, "corpus_GB": round(total_gb, 2), "batch": B, "k": k,
+                  "sources": C, "units_per_rank": [len(u) for u in plan.ranks], "exchange_slots": pipe.slots,
+                  "predicted_ms_per_rank": [round(t, 3) for t in plan.predicted_ms],
+                  "parallelism": f"{C} sources in {sum(len(u.slices) for us in plan.ranks for u in us)} row slices over {world} gpu(s)",
+                  "unit_definition": "queries per second against the whole fixed federation (= federation_queries_per_sec)",
+                  "timing": "ms_per_step = wall clock of the K steps between fences / K; median/p10/p90 (--full) = one HIP-event pair per step"}
+    else:
+        S = len(shards)
+        shape = f"{n} x {d} {args.dtype} rows per shard"
+        layout = (f"{C} shards fixed, {S} per GPU (strong scaling)" if strong else "one shard per GPU (weak scaling)")
+        config = {"workload": f"{shape}, {layout}, query batch {B}, k={k}, exact inner-product top-k + router MLP over "
+                              f"{C} source(s) + cross-shard merge",
+                  "rows_per_shard": n, "dim": d, "batch": B, "k": k, "shards_total": C, "shards_per_gpu": S,
+                  "parallelism": f"shard-per-gpu x{world}" if not strong else f"{C} shards over {world} gpu(s)",
+                  "unit_definition": ("queries per second against the whole fixed federation (= federation_queries_per_sec)" if strong else
+                                      f"(query x {n}-row shard) PAIRS searched per second, whole job = N x federation_queries_per_sec "
+                                      "(N=1: queries/sec on one shard, the BASELINE configuration); federation_queries_per_sec = "
+                                      "queries answered per second against all N shards"),
+                  "timing": "ms_per_step = wall clock of the K steps between fences / K; median/p10/p90 (--full) = one HIP-event pair per step"}
+    res = {"metric": METRIC, "value": round(units * K / elapsed, 1), "unit": "queries/sec", "n_gpus": world, "steps": K,
+           "warmup": args.warmup, "ms_per_step": round(elapsed / K * 1e3, 4), "higher_is_better": True,
+           "scaling": "strong" if fed_mode else args.scaling,
+           "vs_baseline": None, "dtype": args.dtype, "data": "synthetic"}
+    if not args.full:
+        res.update({"federation_queries_per_sec": round(B * K / elapsed, 1), "rccl_ranks": rccl_ranks,
+                    "exchange_backend": (backend if world > 1 else "none (one rank: the merge reads the local buffer)"), "config": config})
+        if last is not None:
+            dump_outputs(args.dump_outputs, *last)
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything beside the headline, after the timed steps ----
     # exchange / merge time per step: a few extra steps AFTER the timed region (the three event records per step stay out of `value`)
     pipe.time_stages(True)
     for _ in range(min(10, max(3, args.steps))):
@@ -282,18 +375,15 @@ def main():
         per_rank = per_rank.view(world, 3).cpu().tolist()
     else:
         per_rank = [mine.cpu().tolist()]
-    rccl_ranks = dist.get_world_size() if (world > 1 and dist.is_initialized()) else 1
 
     sustained = None
     if args.sustained_seconds > 0:
         est = elapsed / args.steps
         n_sus = max(100 if fed_mode else 500, int(args.sustained_seconds / est) + 1)
-        s_elapsed, s_scan_ms, s_launch, _ = timed(n_sus, False)
+        s_elapsed, s_scan_ms, s_launch, _, _ = timed(n_sus, False)
         sustained = (n_sus, s_elapsed, s_scan_ms, s_launch)
 
     if rank == 0:
-        K = args.steps
-        units = B if strong else world * B                 # queries per step the whole job answers (weak: query x shard)
         launches_per_step = n_launch / K
         achieved = alg_bytes * K / (scan_ms * 1e-3) / 1e9
         traffic, traffic_source = None, None
@@ -304,38 +394,9 @@ def main():
                     and tj.get("k", 32) == k and tj.get("lib_version", lib().rr_version()) == lib().rr_version()):
                 traffic = tj.get("hbm_bytes_per_launch")
                 traffic_source = "profiles/traffic.json (static: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload, not measured in this run)"
-        if fed_mode:
-            total_rows = sum(s_.rows for s_ in fed)
-            total_gb = sum(s_.rows * s_.row_bytes for s_ in fed) / 1e9
-            config = {"workload": f"{args.workload}: {C} sources at {'their real row counts' if args.workload_scale == 1 else f'1/{args.workload_scale} of their real row counts'} and encoder widths ({total_rows} rows, {total_gb:.1f} GB fp16), "
-                                  f"{'balanced row slices (placement.plan)' if args.placement == 'sliced' else 'source s -> GPU s mod G'} over {world} GPU(s), "
-                                  f"query batch {B}, k={k}, router MLP + per-unit exact top-k + ONE all_gather + merge",
-                      "dataset": args.workload, "row_scale": f"1/{args.workload_scale}", "placement": args.placement, "rows_total": total_rows, "corpus_GB": round(total_gb, 2), "batch": B, "k": k,
-                      "sources": C, "units_per_rank": [len(u) for u in plan.ranks], "exchange_slots": pipe.slots,
-                      "predicted_ms_per_rank": [round(t, 3) for t in plan.predicted_ms],
-                      "parallelism": f"{C} sources in {sum(len(u.slices) for us in plan.ranks for u in us)} row slices over {world} gpu(s)",
-                      "unit_definition": "queries per second against the whole fixed federation (= federation_queries_per_sec)",
-                      "timing": "ms_per_step = wall clock of the K steps between fences / K; median/p10/p90 = one HIP-event pair per step"}
-        else:
-            S = len(shards)
-            shape = f"{n} x {d} {args.dtype} rows per shard"
-            layout = (f"{C} shards fixed, {S} per GPU (strong scaling)" if strong else "one shard per GPU (weak scaling)")
-            config = {"workload": f"{shape}, {layout}, query batch {B}, k={k}, exact inner-product top-k + router MLP over "
-                                  f"{C} source(s) + cross-shard merge",
-                      "rows_per_shard": n, "dim": d, "batch": B, "k": k, "shards_total": C, "shards_per_gpu": S,
-                      "parallelism": f"shard-per-gpu x{world}" if not strong else f"{C} shards over {world} gpu(s)",
-                      "unit_definition": ("queries per second against the whole fixed federation (= federation_queries_per_sec)" if strong else
-                                          f"(query x {n}-row shard) PAIRS searched per second, whole job = N x federation_queries_per_sec "
-                                          "(N=1: queries/sec on one shard, the BASELINE configuration); federation_queries_per_sec = "
-                                          "queries answered per second against all N shards"),
-                      "timing": "ms_per_step = wall clock of the K steps between fences / K; median/p10/p90 = one HIP-event pair per step"}
         scans = [r[0] for r in per_rank]
         locals_ = [r[1] for r in per_rank]
-        res = {
-            "metric": METRIC, "value": round(units * K / elapsed, 1), "unit": "queries/sec", "n_gpus": world, "steps": K,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / K * 1e3, 4), "higher_is_better": True,
-            "scaling": "strong" if fed_mode else args.scaling,
-            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        res.update({
             "median_ms": round(percentile(per_step, 0.5), 4), "p10_ms": round(percentile(per_step, 0.1), 4),
             "p90_ms": round(percentile(per_step, 0.9), 4),
             "federation_queries_per_sec": round(B * K / elapsed, 1), "exchange_ms": round(exchange_ms, 4), "merge_ms": round(merge_ms, 4),
@@ -355,7 +416,7 @@ def main():
                          "mfma_frac": round(flops * K / (scan_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
                          "scan_share_of_step": round(scan_ms / (elapsed * 1e3), 4),
                          "end_to_end_frac": round(alg_bytes * K / elapsed / 1e9 / HBM_PEAK_GBS, 4)},
-        }
+        })
         if sustained is not None:
             n_sus, s_elapsed, s_scan_ms, s_launch = sustained
             res["roofline"]["sustained"] = {
@@ -365,6 +426,8 @@ def main():
                 "frac": round(alg_bytes * n_sus / (s_scan_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
         if world == 1 and not args.no_cpu_baseline and not fed_mode:
             res["cpu_baseline"] = cpu_baseline(shards[0], xq, n, d, k)
+        if last is not None:
+            dump_outputs(args.dump_outputs, *last)
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.barrier()

@@ -1,13 +1,13 @@
-"""Generates the golden vectors under tests/golden/ by RUNNING THE REFERENCE in this container.
+"""Generates the golden vectors under tests/golden/ by RUNNING THE REFERENCE project from a checkout of it.
 
-    PYTHONPATH=/root/repo python tests/golden/make_golden.py
+    RAGROUTE_REFERENCE_DIR=/path/to/ragroute python tests/golden/make_golden.py
 
-Imports (never copies) /root/reference/ragroute/{rerank,router,data_source}.py.  Only transport and
+Imports (never copies) ragroute/{rerank,router,data_source}.py of that checkout.  Only transport and
 encoder imports are stubbed (zmq, sentence_transformers: no arithmetic in them).  For data_source.py the
 `faiss` import has to be stubbed too — faiss is not installed — so that fixture pins only the GLUE
 (row -> metadata -> text lookups and the returned tuple layout, data_source.py:143-215); the stub's search
-is the CPU oracle on integer-valued data (exact scores).  The reference never travels to the GPU box:
-only the JSON files written here do.
+is the CPU oracle on integer-valued data (exact scores).  The tests need only the JSON files written here, never the
+checkout.
 """
 import json
 import os
@@ -20,7 +20,10 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, "/root/reference")
+REF = os.environ.get("RAGROUTE_REFERENCE_DIR")
+if not REF or not os.path.isdir(os.path.join(REF, "ragroute")):
+    raise SystemExit("set RAGROUTE_REFERENCE_DIR to a checkout of the reference project (the directory holding ragroute/)")
+sys.path.insert(0, REF)
 
 from tests.util import flat_golden_inputs, synth_medrag_corpus, synth_router_case  # noqa: E402
 

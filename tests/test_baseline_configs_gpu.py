@@ -137,8 +137,8 @@ def _bench_line(args, env=None):
 def test_bench_workload_entry_point_is_placement_independent(gpu):
     """bench.py --workload feb4rag at 1/32 of the real row counts: one rank, two ranks on this device (gloo exchange) with the sliced
     and with the whole-source placement - three processes trees, the SAME result checksum, and every N > 1 line carries each rank's
-    scan and local times."""
-    common = ["--workload", "feb4rag", "--workload-scale", "32", "--steps", "3", "--warmup", "1", "--sustained-seconds", "0"]
+    scan and local times (--full: the checksums and per-rank figures are measured beside the headline)."""
+    common = ["--workload", "feb4rag", "--workload-scale", "32", "--steps", "3", "--warmup", "1", "--full", "--sustained-seconds", "0"]
     one = _bench_line(common)
     two = _bench_line(common + ["--gpus", "2"], {"RR_BENCH_BACKEND": "gloo", "RR_BENCH_ONE_DEVICE": "1"})
     whole = _bench_line(common + ["--gpus", "2", "--placement", "whole"], {"RR_BENCH_BACKEND": "gloo", "RR_BENCH_ONE_DEVICE": "1"})
@@ -148,3 +148,32 @@ def test_bench_workload_entry_point_is_placement_independent(gpu):
         assert len(line["per_rank_scan_ms"]["ranks"]) == 2 and len(line["per_rank_local_ms"]["ranks"]) == 2
         assert min(line["per_rank_local_ms"]["ranks"]) > 0 and line["rccl_ranks"] == 2
     assert sum(two["config"]["units_per_rank"]) >= 8 and two["roofline"]["frac"] > 0
+
+
+def test_bench_plain_run_and_dumped_outputs(gpu, tmp_path):
+    """A plain bench run prints the headline line only; --dump-outputs writes the last timed step's answer, the same from run
+    to run, and --full (every extra measurement) computes that same answer: its checksum, taken from the steps after the
+    timed region, is the checksum of the dumped ids."""
+    common = ["--rows", "262144", "--steps", "3", "--warmup", "1"]
+    a = _bench_line(common + ["--dump-outputs", str(tmp_path / "a")])
+    b = _bench_line(common + ["--dump-outputs", str(tmp_path / "b")])
+    full = _bench_line(common + ["--full", "--no-cpu-baseline", "--sustained-seconds", "0", "--dump-outputs", str(tmp_path / "c")])
+    for line in (a, b, full):
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["unit"] == "queries/sec" and line["higher_is_better"] is True and line["dtype"] == "fp16"
+        # value = queries per second of the same timed steps (ms_per_step is rounded to 1e-4 ms)
+        assert abs(line["value"] * line["ms_per_step"] / 256e3 - 1) <= 5e-5 / line["ms_per_step"] + 1e-5
+    for key in ("roofline", "median_ms", "result_checksum", "per_rank_local_ms", "exchange_ms", "cpu_baseline"):
+        assert key not in a, key
+    assert full["roofline"]["frac"] > 0 and full["median_ms"] > 0 and "sustained" not in full["roofline"]
+    S, I = np.load(tmp_path / "a" / "scores.npy"), np.load(tmp_path / "a" / "ids.npy")
+    assert S.dtype == np.float32 and I.dtype == np.float64 and S.shape == I.shape == (256, 32)
+    assert not (tmp_path / "a" / "query_rows.npy").exists()
+    for other in ("b", "c"):
+        assert np.array_equal(S, np.load(tmp_path / other / "scores.npy")) and np.array_equal(I, np.load(tmp_path / other / "ids.npy"))
+    ids = I.astype(np.int64)
+    assert np.array_equal(ids, I) and (((ids >= 0) & (ids < 262144)) | (ids == -1)).all()
+    assert np.isfinite(S).all() and (S[ids == -1] == 0).all()      # padding (-inf, -1) is dumped as (0, -1)
+    assert (np.diff(np.where(ids >= 0, S, -1e30), axis=1) <= 0).all() and (np.diff((ids == -1).astype(int), axis=1) >= 0).all()
+    assert int(ids.sum()) == full["result_checksum"]["ids_sum"]
+    assert round(float(S.astype(np.float64).sum()), 6) == pytest.approx(full["result_checksum"]["score_sum"], abs=1e-5)

@@ -172,29 +172,63 @@ def test_load_router_reads_the_reference_file_formats(tmp_path):
         w.router.load_state_dict(bad)
 
 
-def test_compat_shim_resolves_hot_path_modules_to_ragroute_amd():
-    """compat/ragroute: router/data_source/rerank come from ragroute_amd; other modules fall through to the reference checkout
-    (only checked where one is mounted: it never travels to the GPU box)."""
+def _stand_in_checkout(root, main_py=None):
+    """A minimal stand-in for a checkout of the reference project: the two modules the shim must take from it (config,
+    queue_manager) and, optionally, a main.py.  Written fresh here, so the tests need nothing outside this repository."""
+    pkg = root / "ragroute"
+    pkg.mkdir(parents=True)
+    (pkg / "__init__.py").write_text("")
+    (pkg / "config.py").write_text("K = {'medrag': 32, 'wikipedia': 10}\n")
+    (pkg / "queue_manager.py").write_text("class QueryQueue:\n    pass\n")
+    if main_py is not None:
+        (root / "main.py").write_text(main_py)
+    return str(root)
+
+
+def test_compat_shim_resolves_hot_path_modules_to_ragroute_amd(tmp_path):
+    """compat/ragroute: router/data_source/rerank come from ragroute_amd; other modules fall through to the checkout named by
+    RAGROUTE_REFERENCE_DIR (here a stand-in one)."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    ref = "/root/reference"
+    ref = _stand_in_checkout(tmp_path / "checkout")
     code = ("import ragroute.rerank as r, ragroute.router as ro, ragroute.data_source as ds\n"
             "assert r.rerank_medrag.__module__ == 'ragroute_amd.rerank'\n"
             "assert ro.Router.__module__ == 'ragroute_amd.router' and ds.DataSource.__module__ == 'ragroute_amd.data_source'\n"
             "import os\n"
-            "if os.environ.get('RAGROUTE_REFERENCE_DIR'):\n"
-            "    import ragroute.config as c, ragroute.queue_manager as q\n"
-            "    assert c.__file__.startswith(os.environ['RAGROUTE_REFERENCE_DIR']) and c.K['medrag'] == 32\n"
-            "    assert q.QueryQueue.__module__ == 'ragroute.queue_manager'\n"
+            "import ragroute.config as c, ragroute.queue_manager as q\n"
+            "assert c.__file__.startswith(os.environ['RAGROUTE_REFERENCE_DIR']) and c.K['medrag'] == 32\n"
+            "assert q.QueryQueue.__module__ == 'ragroute.queue_manager'\n"
             "print('shim ok')\n")
-    env = dict(os.environ, PYTHONPATH=os.path.join(root, "compat") + os.pathsep + root)
-    if os.path.isdir(os.path.join(ref, "ragroute")):
-        env["RAGROUTE_REFERENCE_DIR"] = ref
-    else:
-        env.pop("RAGROUTE_REFERENCE_DIR", None)
+    env = dict(os.environ, PYTHONPATH=os.path.join(root, "compat") + os.pathsep + root, RAGROUTE_REFERENCE_DIR=ref)
     res = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
     assert res.returncode == 0 and "shim ok" in res.stdout, res.stderr[-1500:]
+
+
+def test_run_main_executes_the_checkouts_main_py_with_the_drop_ins(tmp_path):
+    """compat/run_main.py runs the checkout's main.py as __main__, arguments passed through, with `ragroute` resolving to the
+    shim (hot-path modules from ragroute_amd) even though main.py's own directory holds a `ragroute` package."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    main_py = ("import sys\n"
+               "import ragroute.router, ragroute.data_source, ragroute.rerank, ragroute.config\n"
+               "assert __name__ == '__main__'\n"
+               "print('argv', sys.argv[1:], sys.argv[0])\n"
+               "print('modules', ragroute.router.Router.__module__, ragroute.data_source.DataSource.__module__,\n"
+               "      ragroute.rerank.rerank_medrag.__module__, ragroute.config.K['medrag'])\n")
+    ref = _stand_in_checkout(tmp_path / "checkout", main_py)
+    env = dict(os.environ, RAGROUTE_REFERENCE_DIR=ref)
+    env.pop("PYTHONPATH", None)
+    res = subprocess.run([sys.executable, os.path.join(root, "compat", "run_main.py"), "--dataset", "medrag", "--simulate"],
+                         cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stderr[-1500:]
+    assert f"argv ['--dataset', 'medrag', '--simulate'] {os.path.join(ref, 'main.py')}" in res.stdout, res.stdout
+    assert "modules ragroute_amd.router ragroute_amd.data_source ragroute_amd.rerank 32" in res.stdout, res.stdout
+    env.pop("RAGROUTE_REFERENCE_DIR")
+    res = subprocess.run([sys.executable, os.path.join(root, "compat", "run_main.py")], cwd=str(tmp_path), env=env,
+                         capture_output=True, text=True, timeout=120)
+    assert res.returncode != 0 and "RAGROUTE_REFERENCE_DIR" in res.stderr
 
 
 # ---- list-shaped merges run on the HOST, like the reference's (rerank.py:3-9, 28-34; called from http_server.py:288-293) ----

@@ -50,18 +50,18 @@ case $task in
 suite)
   timeout -k 10 1000 python -m pytest tests -x -q -m gpu > $O/pytest_gpu.log 2>&1; rc=$?; tail -5 $O/pytest_gpu.log; [ $rc -ne 0 ] && exit $rc
   timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail $O/smoke.log; exit 1; }; tail -1 $O/smoke.log
-  timeout -k 10 300 python bench.py --steps $STEPS --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err || { tail $O/bench_n1.err; exit 1; }
-  RR_BENCH_BACKEND=gloo RR_BENCH_ONE_DEVICE=1 timeout -k 10 300 python bench.py --gpus 2 --steps 10 --warmup 2 --rows 2000000 --sustained-seconds 0 > $O/bench_gloo2_weak.json 2> $O/bench_w2.err || { tail $O/bench_w2.err; exit 1; }
-  RR_BENCH_BACKEND=gloo RR_BENCH_ONE_DEVICE=1 timeout -k 10 300 python bench.py --gpus 2 --steps 10 --warmup 2 --rows 1000000 --scaling strong --sustained-seconds 0 > $O/bench_gloo2_strong.json 2> $O/bench_s2.err || { tail $O/bench_s2.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps $STEPS --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err || { tail $O/bench_n1.err; exit 1; }
+  RR_BENCH_BACKEND=gloo RR_BENCH_ONE_DEVICE=1 timeout -k 10 300 python bench.py --full --gpus 2 --steps 10 --warmup 2 --rows 2000000 --sustained-seconds 0 > $O/bench_gloo2_weak.json 2> $O/bench_w2.err || { tail $O/bench_w2.err; exit 1; }
+  RR_BENCH_BACKEND=gloo RR_BENCH_ONE_DEVICE=1 timeout -k 10 300 python bench.py --full --gpus 2 --steps 10 --warmup 2 --rows 1000000 --scaling strong --sustained-seconds 0 > $O/bench_gloo2_strong.json 2> $O/bench_s2.err || { tail $O/bench_s2.err; exit 1; }
   last $O/bench_n1.json $O/bench_gloo2_weak.json $O/bench_gloo2_strong.json ;;
 tests)
   timeout -k 10 1000 python -m pytest "$@" -m gpu -x -q > $O/pytest.log 2>&1; rc=$?; tail -12 $O/pytest.log; exit $rc ;;
 profiles)
   VER=$(python -c "from ragroute_amd._lib import lib; print(lib().rr_version())")
-  python bench.py --steps $STEPS --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err || { tail $O/bench_n1.err; exit 1; }
-  (cd /tmp && rocprofv3 --kernel-trace --stats -d $R/$O/bench_trace -o t --output-format csv -- python3 $R/bench.py --steps $STEPS --warmup 5 --no-cpu-baseline --sustained-seconds 0 > $R/$O/bench_n1_under_rocprof.json 2> $R/$O/bench_prof.err) || { tail $O/bench_prof.err; exit 1; }
-  (cd /tmp && rocprofv3 --pmc FETCH_SIZE -d $R/$O/pmc_fetch -o t --output-format csv -- python3 $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --sustained-seconds 0 > $R/$O/pmc_fetch.log 2>&1) || exit 1
-  (cd /tmp && rocprofv3 --pmc WRITE_SIZE -d $R/$O/pmc_write -o t --output-format csv -- python3 $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --sustained-seconds 0 > $R/$O/pmc_write.log 2>&1) || exit 1
+  python bench.py --full --steps $STEPS --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err || { tail $O/bench_n1.err; exit 1; }
+  (cd "$(mktemp -d)" && rocprofv3 --kernel-trace --stats -d $R/$O/bench_trace -o t --output-format csv -- python3 $R/bench.py --full --steps $STEPS --warmup 5 --no-cpu-baseline --sustained-seconds 0 > $R/$O/bench_n1_under_rocprof.json 2> $R/$O/bench_prof.err) || { tail $O/bench_prof.err; exit 1; }
+  (cd "$(mktemp -d)" && rocprofv3 --pmc FETCH_SIZE -d $R/$O/pmc_fetch -o t --output-format csv -- python3 $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --sustained-seconds 0 > $R/$O/pmc_fetch.log 2>&1) || exit 1
+  (cd "$(mktemp -d)" && rocprofv3 --pmc WRITE_SIZE -d $R/$O/pmc_write -o t --output-format csv -- python3 $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --sustained-seconds 0 > $R/$O/pmc_write.log 2>&1) || exit 1
   F=$(find $O/pmc_fetch -name '*counter_collection.csv' | head -1); W=$(find $O/pmc_write -name '*counter_collection.csv' | head -1)
   python tools/pmc_traffic.py $F $W 9 $O/traffic.json 10000000 768 256 32 fp16 $VER || exit 1
   IFS=';' read -ra SH <<< "$SHAPES"
@@ -116,9 +116,9 @@ PY
   ;;
 workload)
   for ds in feb4rag medrag; do
-    timeout -k 10 300 python bench.py --workload $ds --steps 10 --warmup 3 --sustained-seconds 0 > $O/bench_${ds}_n1.json 2> $O/bench_${ds}_n1.err || tail -5 $O/bench_${ds}_n1.err
-    RR_BENCH_BACKEND=gloo RR_BENCH_ONE_DEVICE=1 timeout -k 10 400 python bench.py --workload $ds --gpus 2 --steps 10 --warmup 3 --sustained-seconds 0 > $O/bench_${ds}_gloo2.json 2> $O/bench_${ds}_gloo2.err || tail -5 $O/bench_${ds}_gloo2.err
-    RR_BENCH_BACKEND=gloo RR_BENCH_ONE_DEVICE=1 timeout -k 10 400 python bench.py --workload $ds --placement whole --gpus 2 --steps 10 --warmup 3 --sustained-seconds 0 > $O/bench_${ds}_gloo2_whole.json 2> $O/bench_${ds}_gloo2_whole.err || tail -5 $O/bench_${ds}_gloo2_whole.err
+    timeout -k 10 300 python bench.py --full --workload $ds --steps 10 --warmup 3 --sustained-seconds 0 > $O/bench_${ds}_n1.json 2> $O/bench_${ds}_n1.err || tail -5 $O/bench_${ds}_n1.err
+    RR_BENCH_BACKEND=gloo RR_BENCH_ONE_DEVICE=1 timeout -k 10 400 python bench.py --full --workload $ds --gpus 2 --steps 10 --warmup 3 --sustained-seconds 0 > $O/bench_${ds}_gloo2.json 2> $O/bench_${ds}_gloo2.err || tail -5 $O/bench_${ds}_gloo2.err
+    RR_BENCH_BACKEND=gloo RR_BENCH_ONE_DEVICE=1 timeout -k 10 400 python bench.py --full --workload $ds --placement whole --gpus 2 --steps 10 --warmup 3 --sustained-seconds 0 > $O/bench_${ds}_gloo2_whole.json 2> $O/bench_${ds}_gloo2_whole.err || tail -5 $O/bench_${ds}_gloo2_whole.err
     timeout -k 10 400 python tools/config34.py $ds 10 --plan 8 --with-one > $O/plan8_$ds.json 2> $O/plan8_$ds.err || tail -5 $O/plan8_$ds.err
     python -c "
 import json; j = json.loads(open('$O/plan8_$ds.json').read().strip().splitlines()[-1]); print('$ds plan 8: max/mean', j['max_over_mean'], 'max ms', j['max_ms'], 'one GPU ms', j.get('one_gpu_ms'), 'speedup', j.get('predicted_speedup_at_G'), j.get('merged_G_ranks_equal_one_gpu'))"
