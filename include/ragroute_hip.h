@@ -80,7 +80,8 @@ size_t rr_flat_search_workspace_bytes_for(int k, int dim);
  * (-inf, -1) as FAISS pads.
  *   d_xb     device [n_rows][dim] f16/bf16, dim == rr_padded_dim(d) (zero padded)
  *   d_xq     device [nq][dim] same dtype
- *   d_D      device f32 [nq][k]  scores (inner products, f32 accumulation)
+ *   d_D      device f32 [nq][k]  scores (inner products, f32 accumulation) of the ROUNDED corpus and queries: the results are
+ *            exact for the f16/bf16 copies; for the reference's f32 results see rr_flat_search_faithful below
  *   d_I      device i64 [nq][k]  row ids + id_offset (shard base), or -1
  *   d_ws     device workspace of at least rr_flat_search_workspace_bytes(k) bytes
  *   d_route_mask  optional device u8, one byte per query at d_route_mask[q * mask_stride]: 0 means the router
@@ -151,6 +152,38 @@ int rr_flat_search_screened(const void* d_xb, int dtype, const void* d_x8, const
                             const void* d_xq, int nq, int k, int list_len, float* d_D, int64_t* d_I, int64_t id_offset,
                             uint8_t* d_exact, void* d_ws, size_t ws_bytes, const uint8_t* d_route_mask, int64_t mask_stride,
                             void* stream);
+
+/* ---- Optional: f32-faithful exact search ------------------------------------------------------------------------------
+ * Same call site as rr_flat_search_segments (`index.search`, ragroute/data_source.py:158,186,203), but the results are those
+ * of the reference's IndexFlatIP on the UNROUNDED f32 rows and queries (faiss.read_index keeps f32 rows, data_source.py:71):
+ * D[q][j] is the f32 rounding of the f64 sum, in ascending element order, of the f32 x f32 products; rows by D descending,
+ * ties by ascending matrix row (= ascending id when the id_offsets ascend with the segments, as in rr_flat_search_segments);
+ * padding (-inf, -1); rows holding a NaN are never returned.  The corpus keeps its f32 rows beside the f16/bf16 copy (3x the
+ * half bytes).  A search scans the half copy for the list_len best rows per query, re-scores them from the f32 rows and checks a
+ * rigorous bound on the half-precision scan's error (DESIGN.md "f32-faithful mode"): d_exact[q] = 1 means the k rows returned
+ * for q are proven; 0 means the caller must repeat q (a longer list, then rr_flat_search_f32_exact).  Inner product / cosine
+ * only (for cosine, pass rows and queries normalised by rr_l2_normalize_f32).  n_rows_total < 2^32 - 32.
+ *   rr_faithful_build   d_stats f32[4] (error and norm maxima) from the f32 rows d_xf32 [n_rows][ld_f32] (d values used) and
+ *                       their half copy d_xb [n_rows][dim]; rebuild after the corpus changes
+ *   rr_flat_search_faithful  arguments of rr_flat_search_segments (a plain index is one segment), plus d_xf32 / ld_f32 / d (row
+ *                       width of the f32 rows), d_stats, d_xq_f32 f32 [nq][d] (the queries the half d_xq was made from),
+ *                       list_len in [k, 1024], d_exact u8 [nq], d_eps optional f32 [nq] (the bound eps(q), for tests), and
+ *                       a workspace of rr_flat_search_faithful_workspace_bytes(k, list_len, nq, dim) bytes (0 = invalid sizes)
+ *   rr_flat_search_f32_exact  the exact f32 brute-force scan (the proof's last resort): queries qidx[0 .. n_idx) of d_xq_f32
+ *                       [nq][d] (qidx device i32, NULL = queries 0 .. n_idx), each written to its own row of d_D / d_I [nq][k];
+ *                       same segments, route mask and results as rr_flat_search_faithful; workspace
+ *                       rr_flat_search_f32_exact_workspace_bytes(k, d) bytes.  Any k <= 1024, any row count, d <= 8192. */
+int rr_faithful_build(const float* d_xf32, int64_t ld_f32, const void* d_xb, int dtype, int64_t n_rows, int d, int dim, float* d_stats,
+                      void* stream);
+size_t rr_flat_search_faithful_workspace_bytes(int k, int list_len, int nq, int dim);
+int rr_flat_search_faithful(const void* d_xb, int dtype, const float* d_xf32, int64_t ld_f32, const float* d_stats, int64_t n_rows_total,
+                            int d, int dim, const rr_segment* segs, int n_segs, const void* d_xq, const float* d_xq_f32, int nq, int k,
+                            int list_len, float* d_D, int64_t* d_I, uint8_t* d_exact, float* d_eps, void* d_ws, size_t ws_bytes,
+                            const uint8_t* d_route_mask, int64_t mask_stride, void* stream);
+size_t rr_flat_search_f32_exact_workspace_bytes(int k, int d);
+int rr_flat_search_f32_exact(const float* d_xf32, int64_t ld_f32, int64_t n_rows_total, int d, const rr_segment* segs, int n_segs,
+                             const float* d_xq_f32, int nq, const int32_t* d_qidx, int n_idx, int k, float* d_D, int64_t* d_I, void* d_ws,
+                             size_t ws_bytes, const uint8_t* d_route_mask, int64_t mask_stride, void* stream);
 
 /* Measurement aid (bench.py): between rr_profile_begin and rr_profile_end every launch of the scan
  * kernel made by rr_flat_search on the calling thread is bracketed by HIP events on the launch stream.

@@ -145,7 +145,7 @@ const char kBuildFlags[] = "unknown (not built by ragroute_amd/_build.py)";
 
 extern "C" {
 
-int rr_version(void) { return 500; }  // 0.5.0: row-split wide-row kernel for L2 / any k / 193+ queries (8 candidate buffers per workgroup on wide rows at every k: larger workspace), tuning variables ignored by product builds, cursor-free plain scans
+int rr_version(void) { return 600; }  // 0.6.0: f32-faithful exact search (rr_flat_search_faithful, rr_flat_search_f32_exact); 0.5.0: row-split wide-row kernel for L2 / any k / 193+ queries (8 candidate buffers per workgroup on wide rows at every k: larger workspace), tuning variables ignored by product builds, cursor-free plain scans
 const char* rr_build_flags(void) { return kBuildFlags; }
 const char* rr_last_error(void) { return g_err; }
 int rr_device_cus(void) {
@@ -342,27 +342,24 @@ int rr_flat_search_l2(const void* xb, const float* half_sqnorm, int dtype, int64
                           half_sqnorm ? half_sqnorm : &kEmpty, stream);
 }
 
-int rr_flat_search_segments(const void* xb, int dtype, int64_t n_rows_total, int dim, const rr_segment* segs, int n_segs,
-                            const void* xq, int nq, int k, float* D, int64_t* I, void* ws, size_t ws_bytes,
-                            const uint8_t* route_mask, int64_t mask_stride, void* stream) {
-  if (dtype != RR_DTYPE_F16 && dtype != RR_DTYPE_BF16) return fail(RR_ERR_INVALID, "rr_flat_search_segments: bad dtype%s");
-  if (n_segs < 1 || n_segs > RR_MAX_SEGMENTS || !segs) return fail(RR_ERR_INVALID, "rr_flat_search_segments: need 1 .. 32 segments%s");
-  if (n_rows_total < 0 || n_rows_total > 0xFFFFFFE0ll) return fail(RR_ERR_INVALID, "rr_flat_search_segments: bad total row count%s");
-  rr::SegHost h;
+// Validate a segment table and fill the scan's host-side description of it.  `who` names the entry point in the messages.
+static int seg_host_from(const rr_segment* segs, int n_segs, int64_t n_rows_total, const uint8_t* route_mask, int64_t mask_stride,
+                         const char* who, rr::SegHost& h, int64_t& scanned) {
+  if (n_segs < 1 || n_segs > RR_MAX_SEGMENTS || !segs) return fail(RR_ERR_INVALID, "%s: need 1 .. 32 segments", who);
+  if (n_rows_total < 0 || n_rows_total > 0xFFFFFFE0ll) return fail(RR_ERR_INVALID, "%s: bad total row count", who);
   memset(&h, 0, sizeof(h));
   h.n = (uint32_t)n_segs;
-  int64_t prev_end = 0, valid_rows = 0;
+  int64_t prev_end = 0;
   int max_col = -1;
   for (int s = 0; s < n_segs; ++s) {
     const rr_segment& g = segs[s];
     // (row_begin <= n_rows_total is checked first, so the subtraction cannot overflow whatever n_rows is)
     if (g.n_rows < 0 || g.row_begin < prev_end || g.row_begin % RR_SEGMENT_ALIGN != 0 || g.row_begin > n_rows_total ||
         g.n_rows > n_rows_total - g.row_begin)
-      return fail(RR_ERR_INVALID, "rr_flat_search_segments: segments must be ascending, non-overlapping, inside the matrix, and begin at "
-                                  "multiples of 256 rows%s");
-    if (g.mask_col < -1) return fail(RR_ERR_INVALID, "rr_flat_search_segments: mask_col must be >= -1%s");
+      return fail(RR_ERR_INVALID, "%s: segments must be ascending, non-overlapping, inside the matrix, and begin at "
+                                  "multiples of 256 rows", who);
+    if (g.mask_col < -1) return fail(RR_ERR_INVALID, "%s: mask_col must be >= -1", who);
     prev_end = g.row_begin + g.n_rows;
-    valid_rows += g.n_rows;
     if (g.mask_col > max_col) max_col = g.mask_col;
     h.row_begin[s] = (uint32_t)g.row_begin;
     h.row_limit[s] = (uint32_t)prev_end;
@@ -370,16 +367,168 @@ int rr_flat_search_segments(const void* xb, int dtype, int64_t n_rows_total, int
     h.id_offset[s] = g.id_offset;
   }
   if (route_mask && max_col >= 0 && mask_stride <= max_col)
-    return fail(RR_ERR_INVALID, "rr_flat_search_segments: mask_stride must exceed every mask_col%s");
+    return fail(RR_ERR_INVALID, "%s: mask_stride must exceed every mask_col", who);
   // segment s owns the tiles up to the next segment's first row (its alignment gap included); the last one runs to the end of
   // the rows that are scanned at all: nothing behind the last valid row is read
-  const int64_t scanned = prev_end;
+  scanned = prev_end;
   for (int s = 0; s < n_segs; ++s) {
     const int64_t next = s + 1 < n_segs ? segs[s + 1].row_begin : scanned;
     h.tile_end[s] = (uint32_t)((next + rr::kTileRows - 1) / rr::kTileRows);
   }
-  (void)valid_rows;
+  return RR_OK;
+}
+
+int rr_flat_search_segments(const void* xb, int dtype, int64_t n_rows_total, int dim, const rr_segment* segs, int n_segs,
+                            const void* xq, int nq, int k, float* D, int64_t* I, void* ws, size_t ws_bytes,
+                            const uint8_t* route_mask, int64_t mask_stride, void* stream) {
+  if (dtype != RR_DTYPE_F16 && dtype != RR_DTYPE_BF16) return fail(RR_ERR_INVALID, "rr_flat_search_segments: bad dtype%s");
+  rr::SegHost h;
+  int64_t scanned = 0;
+  const int rc = seg_host_from(segs, n_segs, n_rows_total, route_mask, mask_stride, "rr_flat_search_segments", h, scanned);
+  if (rc != RR_OK) return rc;
   return flat_search_impl(xb, dtype, scanned, dim, xq, nq, k, D, I, 0, ws, ws_bytes, route_mask, mask_stride, nullptr, stream, &h);
+}
+
+// ---- f32-faithful exact search -----------------------------------------------------------------------------------------
+static rr::FaithSegs faith_segs(const rr::SegHost& h) {
+  rr::FaithSegs f;
+  memset(&f, 0, sizeof(f));
+  f.n = h.n;
+  for (uint32_t s = 0; s < h.n; ++s) {
+    f.row_begin[s] = h.row_begin[s];
+    f.row_limit[s] = h.row_limit[s];
+    f.mask_col[s] = h.mask_col[s];
+    f.id_offset[s] = h.id_offset[s];
+  }
+  return f;
+}
+
+int rr_faithful_build(const float* xf32, int64_t ld_f32, const void* xb, int dtype, int64_t n_rows, int d, int dim, float* stats,
+                      void* stream) {
+  if (n_rows < 0 || d < 1 || d > dim || ld_f32 < d || rr::scan_padded_dim(dim) != dim || !stats || ((!xf32 || !xb) && n_rows > 0))
+    return fail(RR_ERR_INVALID, "rr_faithful_build: bad arguments%s");
+  if (dtype != RR_DTYPE_F16 && dtype != RR_DTYPE_BF16) return fail(RR_ERR_INVALID, "rr_faithful_build: bad dtype%s");
+  hipError_t e = rr::launch_faithful_build(xf32, ld_f32, xb, dtype, n_rows, d, dim, (uint32_t*)stats, (hipStream_t)stream);
+  return e == hipSuccess ? RR_OK : hip_fail(e, "rr_faithful_build");
+}
+
+struct FaithWs { float* eps; float* PL; int64_t* IL; char* inner; size_t inner_bytes, total; };
+static FaithWs carve_faithful(char* base, int list_len, int nq, int dim, int grid) {
+  FaithWs w;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return base ? base + o : (char*)nullptr; };
+  w.eps = (float*)take((size_t)nq * sizeof(float));
+  w.PL = (float*)take((size_t)nq * list_len * sizeof(float));
+  w.IL = (int64_t*)take((size_t)nq * list_len * sizeof(int64_t));
+  w.inner_bytes = carve(nullptr, list_len, grid, dim).total;
+  w.inner = take(w.inner_bytes);
+  w.total = off;
+  return w;
+}
+
+size_t rr_flat_search_faithful_workspace_bytes(int k, int list_len, int nq, int dim) {
+  if (k < 1 || list_len < k || list_len > rr::kMaxK || nq < 0 || rr::scan_padded_dim(dim) != dim) return 0;
+  const int grid = device_cus();
+  if (grid <= 0) return 0;
+  return carve_faithful(nullptr, list_len, nq, dim, grid).total;
+}
+
+int rr_flat_search_faithful(const void* xb, int dtype, const float* xf32, int64_t ld_f32, const float* stats, int64_t n_rows_total,
+                            int d, int dim, const rr_segment* segs, int n_segs, const void* xq, const float* xq_f32, int nq, int k,
+                            int list_len, float* D, int64_t* I, uint8_t* exact, float* eps, void* ws, size_t ws_bytes,
+                            const uint8_t* route_mask, int64_t mask_stride, void* stream) {
+  using namespace rr;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype != RR_DTYPE_F16 && dtype != RR_DTYPE_BF16) return fail(RR_ERR_INVALID, "rr_flat_search_faithful: bad dtype%s");
+  if (k < 1 || list_len < k || list_len > kMaxK) return fail(RR_ERR_INVALID, "rr_flat_search_faithful: need 1 <= k <= list_len <= 1024%s");
+  if (scan_padded_dim(dim) != dim) return fail(RR_ERR_UNSUPPORTED, "rr_flat_search_faithful: dim must equal rr_padded_dim(d)%s");
+  if (d < 1 || d > dim || ld_f32 < d || nq < 0) return fail(RR_ERR_INVALID, "rr_flat_search_faithful: bad sizes%s");
+  SegHost h;
+  int64_t scanned = 0;
+  int rc = seg_host_from(segs, n_segs, n_rows_total, route_mask, mask_stride, "rr_flat_search_faithful", h, scanned);
+  if (rc != RR_OK) return rc;
+  if (nq == 0) return RR_OK;
+  if (!xq || !xq_f32 || !D || !I || !exact || !ws || !stats || ((!xb || !xf32) && scanned > 0))
+    return fail(RR_ERR_INVALID, "rr_flat_search_faithful: null pointer%s");
+  const int grid = device_cus();
+  if (grid <= 0) return fail(RR_ERR_HIP, "rr_flat_search_faithful: no HIP device%s");
+  FaithWs w = carve_faithful((char*)ws, list_len, nq, dim, grid);
+  if (ws_bytes < w.total) return fail(RR_ERR_WORKSPACE, "rr_flat_search_faithful: workspace smaller than rr_flat_search_faithful_workspace_bytes%s");
+  float* e_out = eps ? eps : w.eps;
+  hipError_t e = launch_faithful_queries(xq_f32, xq, dtype, nq, d, dim, (const uint32_t*)stats, e_out, st);
+  if (e != hipSuccess) return hip_fail(e, "rr_flat_search_faithful/queries");
+  // the half rows through the ordinary segmented scan at k' = list_len, listing MATRIX rows (id_offset := row_begin)
+  const FaithSegs fs = faith_segs(h);
+  for (uint32_t s = 0; s < h.n; ++s) h.id_offset[s] = h.row_begin[s];
+  rc = flat_search_impl(xb, dtype, scanned, dim, xq, nq, list_len, w.PL, w.IL, 0, w.inner, w.inner_bytes, route_mask, mask_stride,
+                        nullptr, stream, &h);
+  if (rc != RR_OK) return rc;
+  e = launch_faithful_rescore(xf32, ld_f32, d, xq_f32, nq, list_len, w.PL, w.IL, e_out, k, fs, route_mask, mask_stride, D, I, exact, st);
+  return e == hipSuccess ? RR_OK : hip_fail(e, "rr_flat_search_faithful/rescore");
+}
+
+// exact scan: per block of queries [G][k] lists -> (two-level if G*k > 8192) merge -> [k] -> D / I rows
+struct ExactWs { float *D1, *D2, *D3; int64_t *I1, *I2, *I3; size_t total; };
+static ExactWs carve_exact(char* base, const rr::FaithPlan& p, int k) {
+  ExactWs w;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return base ? base + o : (char*)nullptr; };
+  const size_t l1 = (size_t)p.nqb * p.G * k, l2 = (size_t)p.nqb * ((p.G + p.gs - 1) / p.gs) * k, l3 = (size_t)p.nqb * k;
+  w.D1 = (float*)take(l1 * 4); w.I1 = (int64_t*)take(l1 * 8);
+  w.D2 = (float*)take(l2 * 4); w.I2 = (int64_t*)take(l2 * 8);
+  w.D3 = (float*)take(l3 * 4); w.I3 = (int64_t*)take(l3 * 8);
+  w.total = off;
+  return w;
+}
+
+size_t rr_flat_search_f32_exact_workspace_bytes(int k, int d) {
+  if (k < 1 || k > rr::kMaxK || d < 1 || d > rr::kMaxDim) return 0;
+  const int grid = device_cus();
+  if (grid <= 0) return 0;
+  return carve_exact(nullptr, rr::faithful_plan(k, d, grid, -1), k).total;
+}
+
+int rr_flat_search_f32_exact(const float* xf32, int64_t ld_f32, int64_t n_rows_total, int d, const rr_segment* segs, int n_segs,
+                             const float* xq_f32, int nq, const int32_t* qidx, int n_idx, int k, float* D, int64_t* I, void* ws,
+                             size_t ws_bytes, const uint8_t* route_mask, int64_t mask_stride, void* stream) {
+  using namespace rr;
+  hipStream_t st = (hipStream_t)stream;
+  if (k < 1 || k > kMaxK) return fail(RR_ERR_INVALID, "rr_flat_search_f32_exact: k must be in [1, 1024]%s");
+  if (d < 1 || d > kMaxDim || ld_f32 < d || nq < 0 || n_idx < 0 || (!qidx && n_idx > nq))
+    return fail(RR_ERR_INVALID, "rr_flat_search_f32_exact: bad sizes%s");
+  SegHost h;
+  int64_t scanned = 0;
+  int rc = seg_host_from(segs, n_segs, n_rows_total, route_mask, mask_stride, "rr_flat_search_f32_exact", h, scanned);
+  if (rc != RR_OK) return rc;
+  if (n_idx == 0) return RR_OK;
+  if (!xq_f32 || !D || !I || !ws || (!xf32 && scanned > 0)) return fail(RR_ERR_INVALID, "rr_flat_search_f32_exact: null pointer%s");
+  const int grid = device_cus();
+  if (grid <= 0) return fail(RR_ERR_HIP, "rr_flat_search_f32_exact: no HIP device%s");
+  const FaithPlan p = faithful_plan(k, d, grid, scanned);
+  ExactWs w = carve_exact((char*)ws, p, k);
+  if (ws_bytes < w.total) return fail(RR_ERR_WORKSPACE, "rr_flat_search_f32_exact: workspace smaller than rr_flat_search_f32_exact_workspace_bytes%s");
+  const FaithSegs fs = faith_segs(h);
+  hipError_t e;
+  for (int q0 = 0; q0 < n_idx; q0 += p.nqb) {
+    const int nqb = n_idx - q0 < p.nqb ? n_idx - q0 : p.nqb;
+    e = launch_faithful_scan(p, xf32, ld_f32, d, scanned, xq_f32, qidx, q0, nqb, k, fs, route_mask, mask_stride, w.D1, w.I1, st);
+    if (e != hipSuccess) return hip_fail(e, "rr_flat_search_f32_exact/scan");
+    const float* Dm = w.D1;
+    const int64_t* Im = w.I1;
+    int lists = p.G;
+    if (lists > p.gs) {   // level 1: groups of gs consecutive lists of one query -> [nqb][G / gs][k]
+      const MergeSrc src{w.D1, w.I1, p.gs * k, 1, 0, 0, 0};
+      e = launch_merge_topk(src, nqb * (lists / p.gs), p.gs * k, k, 1, w.D2, w.I2, st);
+      if (e != hipSuccess) return hip_fail(e, "rr_flat_search_f32_exact/merge1");
+      Dm = w.D2; Im = w.I2; lists /= p.gs;
+    }
+    const MergeSrc src{Dm, Im, lists * k, 1, 0, 0, 0};
+    e = launch_merge_topk(src, nqb, lists * k, k, 1, w.D3, w.I3, st);
+    if (e != hipSuccess) return hip_fail(e, "rr_flat_search_f32_exact/merge");
+    e = launch_faithful_emit(w.D3, w.I3, qidx, q0, nqb, k, fs, D, I, st);
+    if (e != hipSuccess) return hip_fail(e, "rr_flat_search_f32_exact/emit");
+  }
+  return RR_OK;
 }
 
 // ---- int8 screening copy ---------------------------------------------------------------------------------

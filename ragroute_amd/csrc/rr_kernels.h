@@ -107,6 +107,32 @@ hipError_t launch_rescore(const void* xb, const void* xq, int dtype, int dim, in
                           const float* qinfo, int k, float* D, int64_t* I, int64_t id_offset, uint8_t* exact, const uint8_t* mask,
                           int64_t mask_stride, hipStream_t st);
 
+// faithful.hip (f32-faithful exact search: f32 rows beside the half copy)
+struct FaithSegs {                    // by value in the kernargs: the segments of the f32 / half matrices (a plain index is one)
+  uint32_t n;
+  uint32_t row_begin[kMaxSegments], row_limit[kMaxSegments];
+  int32_t mask_col[kMaxSegments];     // < 0: served for every query
+  int64_t id_offset[kMaxSegments];
+};
+constexpr size_t kFaithScanLds = 65536;   // dynamic LDS of one exact-scan workgroup: keys + queries of its query block
+inline int pow2_ceil_host(int n) { int p = 1; while (p < n) p <<= 1; return p; }
+// exact scan schedule: nqb queries per launch, G workgroups (merged gs lists at a time by launch_merge_topk), P keys per query
+struct FaithPlan { int nqb, G, gs, P; size_t lds; };
+FaithPlan faithful_plan(int k, int d, int grid, int64_t n_rows);   // n_rows < 0: the largest G any corpus gets
+double faithful_gamma(int dim);
+hipError_t launch_faithful_build(const float* xf, int64_t ld, const void* xb, int dtype, int64_t n, int d, int dim, uint32_t* stats,
+                                 hipStream_t st);
+hipError_t launch_faithful_queries(const float* xq, const void* xqh, int dtype, int nq, int d, int dim, const uint32_t* stats, float* eps,
+                                   hipStream_t st);
+hipError_t launch_faithful_rescore(const float* xf, int64_t ld, int d, const float* xq, int nq, int L, const float* PL, const int64_t* IL,
+                                   const float* eps, int k, const FaithSegs& segs, const uint8_t* mask, int64_t mask_stride, float* D,
+                                   int64_t* I, uint8_t* exact, hipStream_t st);
+hipError_t launch_faithful_scan(const FaithPlan& p, const float* xf, int64_t ld, int d, int64_t n_rows, const float* xq, const int32_t* qidx,
+                                int q0, int nqb, int k, const FaithSegs& segs, const uint8_t* mask, int64_t mask_stride, float* outD,
+                                int64_t* outI, hipStream_t st);
+hipError_t launch_faithful_emit(const float* Din, const int64_t* Iin, const int32_t* qidx, int q0, int nqb, int k, const FaithSegs& segs,
+                                float* D, int64_t* I, hipStream_t st);
+
 // router.hip
 hipError_t launch_router_mlp(const rr_router_weights* w, const float* xq, int nq, float* logits, uint8_t* mask,
                              hipStream_t st);

@@ -243,6 +243,9 @@ class DataSource:
         self._docs_by_key = {}
         self._batcher = None
         self.batch_window_ms = float(os.environ.get("RAGROUTE_BATCH_WINDOW_MS", 0.2))
+        # RAGROUTE_EXACT_F32=1: keep the index file's f32 rows beside the half copy and return the reference's f32 results
+        # (FlatIndex exact_f32; 3x the half bytes of HBM)
+        self.exact_f32 = os.environ.get("RAGROUTE_EXACT_F32", "0") not in ("", "0")
 
     # -- loading (data_source.py:69-80) -------------------------------------------------------------
     def load_faiss_index(self):
@@ -281,7 +284,8 @@ class DataSource:
             index = xb
         else:
             metric = getattr(self, "index_metric", "ip")
-            index = FlatIndex(xb.shape[1], metric=metric, dtype=self.dtype, device=self.pick_device())
+            kw = {"exact_f32": True} if self.exact_f32 else {}
+            index = FlatIndex(xb.shape[1], metric=metric, dtype=self.dtype, device=self.pick_device(), **kw)
             index.reserve(xb.shape[0])
             index.add(xb)
         self.faiss_indexes = index, metadatas

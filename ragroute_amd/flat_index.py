@@ -25,6 +25,129 @@ def _require_gpu():
         raise _lib.RagrouteHipError("ragroute_amd needs a HIP device (torch.cuda.is_available() is False); there is no CPU fallback")
 
 
+def _as_f32_rows(part, device):
+    """A chunk of f32 rows (numpy, np.memmap or tensor) as a contiguous float32 tensor on `device`."""
+    if isinstance(part, np.ndarray):  # also np.memmap: only this chunk is paged in
+        part = np.ascontiguousarray(part, dtype=np.float32)
+        part = torch.from_numpy(part if part.flags.writeable else part.copy())
+    return part.to(device, dtype=torch.float32).contiguous()
+
+
+class _Faithful:
+    """The f32-faithful mode shared by FlatIndex and SegmentedIndex (exact_f32=True; C ABI rr_flat_search_faithful): the f32 rows
+    `_xf` beside the half copy `_xb`, their error / norm maxima `_fstats`, and the search that proves every query's top-k on the
+    f32 rows — a query whose proof fails is repeated with a list of 1024 rows (`faithful_retries` counts those queries), and
+    what is still unproven is answered by the exact f32 scan (`faithful_fallbacks`)."""
+
+    def _faithful_init(self, n_rows):
+        self._xf = torch.zeros((max(1, n_rows), self.d), dtype=torch.float32, device=self.device)
+        self._fstats = torch.zeros(4, dtype=torch.float32, device=self.device)
+        self._ws_faithful = {}
+        self._ws_exact = {}
+        self.faithful_list = None   # rows re-scored per query; None = min(1024, max(256, 4 k))
+        self.faithful_retries = 0
+        self.faithful_fallbacks = 0
+
+    def _ingest_f32(self, x, out_f, out_h, chunk_rows):
+        """f32 rows -> out_f (normalised for cosine by rr_l2_normalize_f32) -> the half copy out_h derived from those rows."""
+        for s in range(0, x.shape[0], chunk_rows):
+            e = min(x.shape[0], s + chunk_rows)
+            f, h = out_f[s:e], out_h[s:e]
+            f.copy_(_as_f32_rows(x[s:e], self.device))
+            if self.metric == "cosine":
+                check(lib().rr_l2_normalize_f32(f.data_ptr(), e - s, self.d, _stream_ptr()), "rr_l2_normalize_f32")
+            check(lib().rr_rows_to_half(f.data_ptr(), e - s, self.d, self.d, h.data_ptr(), _RR_DTYPE[self.dtype], self.dim, 0,
+                                        _stream_ptr()), "rr_rows_to_half")
+
+    def _faithful_build(self, n_rows):
+        check(lib().rr_faithful_build(self._xf.data_ptr(), self.d, self._xb.data_ptr(), _RR_DTYPE[self.dtype], n_rows, self.d, self.dim,
+                                      self._fstats.data_ptr(), _stream_ptr()), "rr_faithful_build")
+
+    def _prepare_f32(self, xq):
+        """float32 [nq,d] -> (half [nq,dim], f32 [nq,d]) device queries (both normalised by the library for cosine)."""
+        if isinstance(xq, np.ndarray):
+            xq = torch.from_numpy(np.ascontiguousarray(xq, dtype=np.float32))
+        if xq.dim() != 2 or xq.shape[1] != self.d:
+            raise ValueError(f"queries must be [nq,{self.d}]")
+        xf = xq.to(self.device, dtype=torch.float32).contiguous()
+        if self.metric == "cosine":
+            xf = xf.clone()
+            check(lib().rr_l2_normalize_f32(xf.data_ptr(), xf.shape[0], self.d, _stream_ptr()), "rr_l2_normalize_f32")
+        xh = torch.empty((xf.shape[0], self.dim), dtype=self._xb.dtype, device=self.device)
+        check(lib().rr_rows_to_half(xf.data_ptr(), xf.shape[0], self.d, self.d, xh.data_ptr(), _RR_DTYPE[self.dtype], self.dim, 0,
+                                    _stream_ptr()), "rr_rows_to_half")
+        return xh, xf
+
+    def _faithful_list_len(self, k):
+        L = self.faithful_list if self.faithful_list is not None else min(_lib.RR_MAX_K, max(256, 4 * k))
+        return max(int(L), k)
+
+    def _faithful_raw(self, xq_half, xq_f32, k, L, segs, n_rows_total, mptr, mstride, D=None, I=None):
+        nq = xq_half.shape[0]
+        key = (k, L, nq)
+        ws = self._ws_faithful.get(key)
+        if ws is None:
+            nbytes = lib().rr_flat_search_faithful_workspace_bytes(k, L, nq, self.dim)
+            if nbytes == 0:
+                raise ValueError(f"need 1 <= k <= list_len <= {_lib.RR_MAX_K}, got k={k}, list_len={L}")
+            self._ws_faithful = {key: torch.empty(nbytes, dtype=torch.uint8, device=self.device)}
+            ws = self._ws_faithful[key]
+        D = torch.empty((nq, k), dtype=torch.float32, device=self.device) if D is None else D
+        I = torch.empty((nq, k), dtype=torch.int64, device=self.device) if I is None else I
+        exact = torch.empty(nq, dtype=torch.uint8, device=self.device)
+        eps = torch.empty(nq, dtype=torch.float32, device=self.device)
+        check(lib().rr_flat_search_faithful(self._xb.data_ptr(), _RR_DTYPE[self.dtype], self._xf.data_ptr(), self.d, self._fstats.data_ptr(),
+                                            n_rows_total, self.d, self.dim, segs, len(segs), xq_half.data_ptr(), xq_f32.data_ptr(), nq, k, L,
+                                            D.data_ptr(), I.data_ptr(), exact.data_ptr(), eps.data_ptr(), ws.data_ptr(), ws.numel(), mptr,
+                                            mstride, _stream_ptr()), "rr_flat_search_faithful")
+        return D, I, exact, eps
+
+    def _exact_scan(self, xq_f32, qidx, k, segs, n_rows_total, mptr, mstride, D, I):
+        ws = self._ws_exact.get(k)
+        if ws is None:
+            nbytes = lib().rr_flat_search_f32_exact_workspace_bytes(k, self.d)
+            if nbytes == 0:
+                raise ValueError(f"k must be in [1, {_lib.RR_MAX_K}], got {k}")
+            self._ws_exact = {k: torch.empty(nbytes, dtype=torch.uint8, device=self.device)}
+            ws = self._ws_exact[k]
+        check(lib().rr_flat_search_f32_exact(self._xf.data_ptr(), self.d, n_rows_total, self.d, segs, len(segs), xq_f32.data_ptr(),
+                                             xq_f32.shape[0], qidx.data_ptr() if qidx is not None else None,
+                                             qidx.numel() if qidx is not None else xq_f32.shape[0], k, D.data_ptr(), I.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), mptr, mstride, _stream_ptr()), "rr_flat_search_f32_exact")
+
+    def _faithful_search(self, xq, k, route_mask, out, segs, n_rows_total, mask_args):
+        """search_exact_f32, then one host read of the proof flags; unproven queries again at list_len = 1024, then the exact scan."""
+        if not (isinstance(xq, tuple) and len(xq) == 2):
+            raise ValueError("an exact_f32 index searches the (half, f32) query pair that prepare_queries() returns")
+        xq_half, xq_f32 = xq
+        if (xq_half.dtype != self._xb.dtype or xq_half.dim() != 2 or xq_half.shape[1] != self.dim or not xq_half.is_contiguous()
+                or xq_f32.dtype != torch.float32 or xq_f32.shape != (xq_half.shape[0], self.d) or not xq_f32.is_contiguous()):
+            raise ValueError("search_prepared() needs the contiguous ([nq, dim] index dtype, [nq, d] float32) pair of prepare_queries()")
+        nq = xq_half.shape[0]
+        D, I = out if out is not None else (None, None)
+        mptr, mstride = mask_args(route_mask, nq)
+        D, I, exact, _ = self._faithful_raw(xq_half, xq_f32, k, self._faithful_list_len(k), segs, n_rows_total, mptr, mstride, D, I)
+        if nq == 0:
+            return D, I
+        bad = torch.nonzero(exact == 0).flatten()
+        if bad.numel() == 0:
+            return D, I
+        self.faithful_retries += int(bad.numel())
+        still = bad
+        if self._faithful_list_len(k) < _lib.RR_MAX_K:
+            sub_mask = route_mask[bad].contiguous() if route_mask is not None else None
+            smptr, smstride = mask_args(sub_mask, int(bad.numel()))
+            D2, I2, ex2, _ = self._faithful_raw(xq_half[bad].contiguous(), xq_f32[bad].contiguous(), k, _lib.RR_MAX_K, segs, n_rows_total,
+                                                smptr, smstride)
+            D[bad] = D2
+            I[bad] = I2
+            still = bad[ex2 == 0]
+        if still.numel():
+            self.faithful_fallbacks += int(still.numel())
+            self._exact_scan(xq_f32, still.to(torch.int32).contiguous(), k, segs, n_rows_total, mptr, mstride, D, I)
+        return D, I
+
+
 def normalize_L2(x):
     """In-place row-wise L2 normalisation (faiss.normalize_L2, data_source.py:198-199).
     Accepts a C-contiguous float32 numpy array [n,d] (normalised in place through the GPU) or a
@@ -42,7 +165,7 @@ def normalize_L2(x):
     x[...] = t.cpu().numpy()
 
 
-class FlatIndex:
+class FlatIndex(_Faithful):
     """Exact inner-product index (the role of faiss.IndexFlatIP in the reference).
 
     metric: "ip" (reference behaviour), "cosine" (rows and queries L2-normalised on ingest/search, i.e. normalize_L2 + IP
@@ -53,11 +176,17 @@ class FlatIndex:
     build_screen() adds an int8 screening copy (ip / cosine, d <= 1536): searches then stream half the bytes and return the
     same exact top-k, proven per query by a quantisation-error bound; a batch whose proof fails is repeated on the
     f16/bf16 rows (counted in `screen_fallbacks`).
+
+    exact_f32=True (ip / cosine): the f32 rows are kept beside the half copy (3x the half bytes) and searches return what the
+    reference's IndexFlatIP returns on the UNROUNDED f32 rows and queries, bit for bit with an f64-accumulating CPU scan: the half
+    copy only screens (include/ragroute_hip.h rr_flat_search_faithful).  prepare_queries() then returns a (half, f32) pair.
     """
 
-    def __init__(self, d, metric="ip", dtype="fp16", device=None):
+    def __init__(self, d, metric="ip", dtype="fp16", device=None, exact_f32=False):
         if metric not in ("ip", "cosine", "l2"):
             raise ValueError(f"unknown metric {metric!r}")
+        if exact_f32 and metric == "l2":
+            raise ValueError("exact_f32 serves the ip / cosine metrics only")
         if dtype not in _TORCH_DTYPE:
             raise ValueError(f"unknown dtype {dtype!r}")
         self.d = int(d)
@@ -76,6 +205,9 @@ class FlatIndex:
         self._ws_screen = {}
         self.screen_list = 512
         self.screen_fallbacks = 0
+        self.exact_f32 = bool(exact_f32)
+        if self.exact_f32:
+            self._faithful_init(0)
 
     # -- storage -----------------------------------------------------------------------------
     def reserve(self, n):
@@ -83,6 +215,10 @@ class FlatIndex:
             new = torch.empty((n, self.dim), dtype=self._xb.dtype, device=self.device)
             new[: self.ntotal].copy_(self._xb[: self.ntotal])
             self._xb = new
+            if self.exact_f32:
+                newf = torch.empty((n, self.d), dtype=torch.float32, device=self.device)
+                newf[: self.ntotal].copy_(self._xf[: self.ntotal])
+                self._xf = newf
 
     def add(self, x, chunk_rows=1 << 18):
         """Append rows (float32 numpy [n,d] or CUDA tensor) to the HBM-resident corpus."""
@@ -91,6 +227,12 @@ class FlatIndex:
             raise ValueError(f"expected rows of dimension {self.d}, got {x.shape[1]}")
         if self.ntotal + n > self._xb.shape[0]:
             self.reserve(max(self.ntotal + n, int(self._xb.shape[0] * 1.5)))
+        if self.exact_f32:
+            with torch.cuda.device(self.device):
+                self._ingest_f32(x, self._xf[self.ntotal: self.ntotal + n], self._xb[self.ntotal: self.ntotal + n], chunk_rows)
+                self.ntotal += n
+                self._faithful_build(self.ntotal)   # maxima over the whole corpus
+            return
         with torch.cuda.device(self.device):
             for s in range(0, n, chunk_rows):
                 e = min(n, s + chunk_rows)
@@ -117,6 +259,8 @@ class FlatIndex:
 
     def adopt(self, xb_dev, ntotal=None):
         """Use an existing device matrix [n, dim] of the index dtype as the corpus (no copy)."""
+        if self.exact_f32:
+            raise _lib.RagrouteHipError("adopt() takes a half matrix only; an exact_f32 index ingests its f32 rows with add()")
         if xb_dev.dtype != self._xb.dtype or xb_dev.dim() != 2 or xb_dev.shape[1] != self.dim or not xb_dev.is_contiguous():
             raise ValueError("adopt() needs a contiguous device matrix [n, rr_padded_dim(d)] of the index dtype")
         self._xb = xb_dev
@@ -129,6 +273,8 @@ class FlatIndex:
         exactly (k <= list_len <= 1024; default max(512, 16 k) capped at 1024)."""
         if self.metric == "l2":
             raise _lib.RagrouteHipError("the int8 screening copy serves the ip / cosine metrics only")
+        if self.exact_f32:
+            raise _lib.RagrouteHipError("the int8 screening copy and exact_f32 do not combine")
         dim8 = lib().rr_screen_dim(self.dim)
         if dim8 < 0:
             raise _lib.RagrouteHipError("the int8 screening copy needs d <= 1536")
@@ -202,7 +348,10 @@ class FlatIndex:
         return ws
 
     def prepare_queries(self, xq):
-        """float32 [nq,d] (numpy or tensor) -> device [nq,dim] in the index dtype (normalised for cosine)."""
+        """float32 [nq,d] (numpy or tensor) -> device [nq,dim] in the index dtype (normalised for cosine).
+        exact_f32: the pair (half [nq,dim], f32 [nq,d]) that search_prepared() takes."""
+        if self.exact_f32:
+            return self._prepare_f32(xq)
         if isinstance(xq, np.ndarray):
             xq = torch.from_numpy(np.ascontiguousarray(xq, dtype=np.float32))
         if xq.dim() != 2 or xq.shape[1] != self.d:
@@ -216,7 +365,10 @@ class FlatIndex:
     def search_prepared(self, xq_half, k, id_offset=0, out=None, route_mask=None):
         """Device-to-device search: xq_half [nq,dim] index dtype -> (D f32[nq,k], I i64[nq,k]) CUDA tensors.
         route_mask: optional bool/uint8 CUDA tensor [nq] (may be a strided column of the router's [nq,C] mask):
-        queries with a zero entry get an all-padding result.  Enqueued on the current stream, no host sync."""
+        queries with a zero entry get an all-padding result.  Enqueued on the current stream, no host sync.
+        exact_f32: xq_half is the (half, f32) pair of prepare_queries(); one host read of the proof flags."""
+        if self.exact_f32:
+            return self._faithful_search(xq_half, k, route_mask, out, self._segments(id_offset, route_mask), self.ntotal, self._mask_args)
         if xq_half.dtype != self._xb.dtype or xq_half.dim() != 2 or xq_half.shape[1] != self.dim or not xq_half.is_contiguous():
             raise ValueError("search_prepared() needs contiguous [nq, dim] queries of the index dtype")
         nq = xq_half.shape[0]
@@ -245,6 +397,20 @@ class FlatIndex:
                   "rr_flat_search")
         return D, I
 
+    def _segments(self, id_offset=0, route_mask=None):
+        return (_lib.SegmentStruct * 1)(_lib.SegmentStruct(0, self.ntotal, int(id_offset), 0 if route_mask is not None else -1, 0))
+
+    def search_exact_f32(self, xq_f32_dev, k, list_len=None, route_mask=None, id_offset=0):
+        """exact_f32 index, device to device, no host sync: float32 queries [nq,d] -> (D, I, exact, eps) CUDA tensors.  exact[q] == 1
+        where the top-k is proven on the f32 rows; eps[q] is the bound on the half-precision scan's error for query q.  search()
+        and search_prepared() wrap this with the retry and the exact fallback."""
+        if not self.exact_f32:
+            raise _lib.RagrouteHipError("search_exact_f32() needs an index built with exact_f32=True")
+        xh, xf = self._prepare_f32(xq_f32_dev)
+        L = self._faithful_list_len(k) if list_len is None else int(list_len)
+        mptr, mstride = self._mask_args(route_mask, xh.shape[0])
+        return self._faithful_raw(xh, xf, int(k), L, self._segments(id_offset, route_mask), self.ntotal, mptr, mstride)
+
     def search(self, xq, k):
         """faiss call shape: float32 [nq,d] -> (D float32[nq,k], I int64[nq,k]) numpy arrays."""
         with torch.cuda.device(self.device):
@@ -252,7 +418,7 @@ class FlatIndex:
             return D.cpu().numpy(), I.cpu().numpy()
 
 
-class SegmentedIndex:
+class SegmentedIndex(_Faithful):
     """Several data sources that are searched with the SAME query embeddings, resident in ONE HBM matrix and searched in ONE
     pass (C ABI `rr_flat_search_segments`): MedRAG's four sources all use MedCPT, five FeB4RAG sources UAE-Large-V1
     (reference ragroute/config.py:37-71).  The reference asks every selected source separately (`index.search`,
@@ -263,15 +429,15 @@ class SegmentedIndex:
     Source s occupies rows [begin_s, begin_s + n_s) of the matrix, begin_s a multiple of 256; `source(s)` is a FlatIndex on that
     slice (no copy), so the per-source call surface (`DataSource.retrieve_docs_*`) keeps working on the same memory.
     Result ids are id_offsets[s] + local row; ties are broken by (source order, row) = ascending id when the id offsets ascend.
-    Metrics: "ip" / "cosine"."""
+    Metrics: "ip" / "cosine".  exact_f32=True: f32 rows beside the half matrix, results faithful to them (FlatIndex)."""
 
-    def __init__(self, d, rows_per_source, id_offsets=None, mask_cols=None, metric="ip", dtype="fp16", device=None):
+    def __init__(self, d, rows_per_source, id_offsets=None, mask_cols=None, metric="ip", dtype="fp16", device=None, exact_f32=False):
         if metric not in ("ip", "cosine"):
             raise ValueError("SegmentedIndex serves the ip / cosine metrics")
         rows = [int(n) for n in rows_per_source]
         if not 1 <= len(rows) <= _lib.RR_MAX_SEGMENTS or min(rows) < 0:
             raise ValueError(f"need 1 .. {_lib.RR_MAX_SEGMENTS} sources with >= 0 rows each")
-        self._proto = FlatIndex(d, metric=metric, dtype=dtype, device=device)   # query conversion, workspace, dims
+        self._proto = FlatIndex(d, metric=metric, dtype=dtype, device=device, exact_f32=exact_f32)   # query conversion, workspace, dims
         self.d, self.dim, self.metric, self.dtype, self.device = self._proto.d, self._proto.dim, metric, dtype, self._proto.device
         self.rows = rows
         self.id_offsets = [int(v) for v in (id_offsets if id_offsets is not None else [s << 40 for s in range(len(rows))])]
@@ -290,6 +456,9 @@ class SegmentedIndex:
         self._segs = (_lib.SegmentStruct * len(rows))(*[_lib.SegmentStruct(b, n, o, c, 0)
                                                         for b, n, o, c in zip(self.begins, rows, self.id_offsets, self.mask_cols)])
         self.ntotal = sum(rows)
+        self.exact_f32 = bool(exact_f32)
+        if self.exact_f32:
+            self._faithful_init(self.n_rows_total)
 
     def rows_of(self, s):
         """Device view [n_s, dim] of source s (fill it with rows in the index dtype, zero padded to dim)."""
@@ -306,6 +475,11 @@ class SegmentedIndex:
         if x.shape[0] != self.rows[s] or x.shape[1] != self.d:
             raise ValueError(f"source {s} holds [{self.rows[s]}, {self.d}] rows")
         out = self.rows_of(s)
+        if self.exact_f32:
+            with torch.cuda.device(self.device):
+                self._ingest_f32(x, self._xf[self.begins[s]: self.begins[s] + self.rows[s]], out, chunk_rows)
+                self._faithful_build(self.n_rows_total)
+            return
         with torch.cuda.device(self.device):
             for b in range(0, x.shape[0], chunk_rows):
                 part = x[b: b + chunk_rows]
@@ -334,7 +508,10 @@ class SegmentedIndex:
 
     def search_prepared(self, xq_half, k, route_mask=None, out=None):
         """xq_half [nq, dim] index dtype -> (D f32 [nq,k], I i64 [nq,k]) CUDA tensors: the merged top-k over the selected sources.
-        route_mask: optional bool/uint8 CUDA matrix [nq, C] (the router's mask; source s reads column mask_cols[s])."""
+        route_mask: optional bool/uint8 CUDA matrix [nq, C] (the router's mask; source s reads column mask_cols[s]).
+        exact_f32: xq_half is the (half, f32) pair of prepare_queries()."""
+        if self.exact_f32:
+            return self._faithful_search(xq_half, k, route_mask, out, self._segs, self.n_rows_total, self._mask_args)
         if xq_half.dtype != self._xb.dtype or xq_half.dim() != 2 or xq_half.shape[1] != self.dim or not xq_half.is_contiguous():
             raise ValueError("search_prepared() needs contiguous [nq, dim] queries of the index dtype")
         nq = xq_half.shape[0]
@@ -344,16 +521,28 @@ class SegmentedIndex:
             I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         else:
             D, I = out
-        mptr, mstride = None, 0
-        if route_mask is not None:
-            if (route_mask.dtype not in (torch.bool, torch.uint8) or route_mask.dim() != 2 or route_mask.shape[0] != nq
-                    or not route_mask.is_cuda or route_mask.stride(1) != 1 or route_mask.shape[1] <= max(self.mask_cols)):
-                raise ValueError("route_mask must be a bool/uint8 CUDA matrix [nq, C] with unit column stride covering every mask column")
-            mptr, mstride = route_mask.data_ptr(), route_mask.stride(0)
+        mptr, mstride = self._mask_args(route_mask, nq)
         check(lib().rr_flat_search_segments(self._xb.data_ptr(), _RR_DTYPE[self.dtype], self.n_rows_total, self.dim, self._segs,
                                             len(self.rows), xq_half.data_ptr(), nq, k, D.data_ptr(), I.data_ptr(), ws.data_ptr(),
                                             ws.numel(), mptr, mstride, _stream_ptr()), "rr_flat_search_segments")
         return D, I
+
+    def _mask_args(self, route_mask, nq):
+        if route_mask is None:
+            return None, 0
+        if (route_mask.dtype not in (torch.bool, torch.uint8) or route_mask.dim() != 2 or route_mask.shape[0] != nq
+                or not route_mask.is_cuda or route_mask.stride(1) != 1 or route_mask.shape[1] <= max(self.mask_cols)):
+            raise ValueError("route_mask must be a bool/uint8 CUDA matrix [nq, C] with unit column stride covering every mask column")
+        return route_mask.data_ptr(), route_mask.stride(0)
+
+    def search_exact_f32(self, xq_f32_dev, k, list_len=None, route_mask=None):
+        """As FlatIndex.search_exact_f32, over the segments (route_mask [nq, C] as search_prepared)."""
+        if not self.exact_f32:
+            raise _lib.RagrouteHipError("search_exact_f32() needs an index built with exact_f32=True")
+        xh, xf = self._prepare_f32(xq_f32_dev)
+        L = self._faithful_list_len(k) if list_len is None else int(list_len)
+        mptr, mstride = self._mask_args(route_mask, xh.shape[0])
+        return self._faithful_raw(xh, xf, int(k), L, self._segs, self.n_rows_total, mptr, mstride)
 
     def search(self, xq, k, route_mask=None):
         """float32 [nq,d] -> (D, I) numpy arrays (merged over the selected sources)."""
