@@ -30,11 +30,10 @@ enum { RR_MAX_K = 1024, RR_QUERY_BLOCK = 256 };
 
 /* Library version (major*10000 + minor*100 + patch). */
 int rr_version(void);
-/* The compiler flags this library was built with (ragroute_amd/_build.py).  A product build carries no -D switch: the
- * development kernels (RR_DEV_VARIANTS) and the timing-only ablations that exist inside such builds are then not compiled
- * in, and a test can tell the library under test from an A/B build.  A product build also reads NO environment variable:
+/* The compiler flags this library was built with (ragroute_amd/_build.py).  A product build carries no -D switch, so a
+ * test can tell the library under test from a development (A/B) build.  A product build reads NO environment variable:
  * the RR_* tuning variables (kernel selection, chunk schedule, sample size, timelines) are honoured by -DRR_DEV_VARIANTS
- * builds only. */
+ * builds only, which compile the same kernels. */
 const char* rr_build_flags(void);
 /* Message of the last failure on the calling thread ("" if none). */
 const char* rr_last_error(void);

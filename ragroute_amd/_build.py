@@ -13,17 +13,17 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 OBJ_DIR = os.path.join(CSRC, "build")
 LIB_PATH = os.path.join(PKG, "libragroute_hip.so")
-SOURCES = ["capi.hip", "flat_scan.hip", "flat_scan_wide.hip", "flat_scan_dev.hip", "select.hip", "prep.hip", "router.hip", "screen.hip", "faithful.hip"]
+SOURCES = ["capi.hip", "flat_scan.hip", "flat_scan_wide.hip", "select.hip", "prep.hip", "router.hip", "screen.hip", "faithful.hip"]
 HEADERS = ["rr_common.h", "rr_kernels.h", "rr_sort.h", "flat_scan_common.h"]
 LLVM_BIN = os.environ.get("RR_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 
 # kernels whose accumulators live in hard-wired AGPRs named only inside asm text
-FIXED_AGPR_KERNELS = ("flat_scan_wide",)   # flat_scan_wide_kernel, _pd_kernel, wide8_kernel
+FIXED_AGPR_KERNELS = ("flat_scan_wide",)   # flat_scan_wide_pd_kernel, flat_scan_wide8_kernel, flat_scan_wide_rs_kernel
 # Scalar-register pressure tripwire for the hand-scheduled kernels: the largest .sgpr_spill_count per kernel family as of round 4
 # (only the L2 four-block instances of the 4-wave kernel spill, 2 SGPRs, outside the counted-wait step).  Spilled SGPRs go to
 # lanes of a compiler-owned VGPR (v_writelane / v_readlane), which is correct but costs issue slots inside a loop whose waits
 # are counted by hand: a count above these is a build failure, to be looked at, not waved through.
-SGPR_SPILL_MAX = {"flat_scan_wide_pd_kernel": 2, "flat_scan_wide8_kernel": 0, "flat_scan_wide_rs_kernel": 0, "flat_scan_wide_kernel": 0}
+SGPR_SPILL_MAX = {"flat_scan_wide_pd_kernel": 2, "flat_scan_wide8_kernel": 0, "flat_scan_wide_rs_kernel": 0}
 
 
 PRODUCT_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17"]   # what rr_build_flags() of a product library reports
@@ -31,12 +31,8 @@ PRODUCT_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17"]   # what
 
 def _flags():
     flags = list(PRODUCT_FLAGS)
-    if os.environ.get("RR_DEV_VARIANTS") or os.environ.get("RR_ABLATION_VARIANTS"):
-        flags.append("-DRR_DEV_VARIANTS")      # the measured alternatives of flat_scan_dev.hip (RR_SCAN_VARIANT / RR_GENERIC_TALL)
-    if os.environ.get("RR_ABLATION_VARIANTS"):
-        flags.append("-DRR_ABLATION_VARIANTS")  # + timing-only ablations of the 32x32x16 loop
-    if os.environ.get("RR_EXTRA_DEFINES"):      # development A/B builds, e.g. "-DRR_DMA_SCHED=1"
-        flags += os.environ["RR_EXTRA_DEFINES"].split()
+    if os.environ.get("RR_DEV_VARIANTS"):
+        flags.append("-DRR_DEV_VARIANTS")      # the library honours the RR_* tuning variables (rr::tuning_env)
     return flags
 
 
@@ -152,8 +148,7 @@ def build(force=False, verbose=False):
     lib_path = LIB_PATH.replace(".so", suffix + ".so") if suffix else LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = _flags()
-    # objects of a suffixed (development / A/B) library live in their own directory: "flat_scan" + "_dev" must not meet the
-    # product object of flat_scan_dev.hip
+    # objects of a suffixed (development / A/B) library live in their own directory
     obj_dir = os.path.join(OBJ_DIR, suffix.strip("_")) if suffix else OBJ_DIR
     os.makedirs(obj_dir, exist_ok=True)
     headers = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(PKG, "..", "include", "ragroute_hip.h")]

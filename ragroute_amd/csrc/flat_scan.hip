@@ -23,10 +23,10 @@
 //   flat_scan16_kernel      D <= 768: 16x16x32 MFMA, hand-pipelined asm loop, nt LDS-DMA, optional L2 metric; also the int8
 //                           screening copy (I8Pair, v_mfma_i32_16x16x64_i8)
 //   flat_scan16h_kernel     768 < D <= 1536, up to 128 queries: 32 resident queries per wave, half-tile LDS ring
-//   flat_scan_wide_kernel   D > 1536, and more than 128 queries (or the L2 metric) at 768 < D <= 1536: accumulators resident
-//                           in AGPRs, corpus by LDS-DMA, queries streamed from L2
-// The measured alternatives (32x32x16 shape, compiler-scheduled loop, two waves per SIMD, compiler-scheduled wide-row forms,
-// stamped / ablation builds) live in flat_scan_dev.hip and are compiled only with RR_DEV_VARIANTS=1 (see _build.py).
+//   flat_scan_wide_*_kernel D > 1536, and more than 128 queries (or the L2 metric) at 768 < D <= 1536 (flat_scan_wide.hip):
+//                           accumulators resident in AGPRs, corpus by LDS-DMA, queries streamed from L2
+// The alternatives that were measured and lost (32x32x16 shape, compiler-scheduled loop, two waves per SIMD, compiler-scheduled
+// wide-row forms) are recorded in DESIGN_HISTORY.md.
 #include "flat_scan_common.h"
 
 namespace rr {
@@ -34,9 +34,6 @@ namespace rr {
 // L2 = true ranks by  q.x - |x|^2/2  (descending == ascending squared L2 distance): the per-row |x|^2/2 of a tile is
 // one more 256-byte LDS-DMA piece (issued by wave 0, ahead of the tile-after-next's pieces so the in-order vmcnt wait of
 // the tile covers it) and the epilogue subtracts it before the filter.
-#ifndef RR_SCAN_STAGGER
-#define RR_SCAN_STAGGER 0
-#endif
 // SEG = true: the launch is a chunk of a segmented search (a.ranges: one run of tiles per segment, a TileCursor per stream).  Plain
 // searches run the SEG = false instantiation, whose tile arithmetic and epilogue carry nothing of that (round 4: the same-device
 // A/B against round 2's kernel priced the run-time form at 0.5 - 0.8 % of the headline's scan launch, profiles/r04/headline_ab.json).
@@ -58,7 +55,7 @@ __global__ __launch_bounds__(256, 1) void flat_scan16_kernel(const ScanArgs a) {
   const int col = lane & 15, g = lane >> 4;
   if (a.timeline && threadIdx.x == 0) a.timeline[blockIdx.x] = __builtin_amdgcn_s_memrealtime();  // diagnostics only
 
-  // ---- LDS image (identical to flat_scan_kernel's).  A fragment (rb, s2): row rb*16 + col, chunk 4*(s2&1) + g of
+  // ---- LDS image.  A fragment (rb, s2): row rb*16 + col, chunk 4*(s2&1) + g of
   // k group s2>>1 -------------------------------------------------------------------------------------------------
   uint32_t roff[2][2];
   {
@@ -169,12 +166,6 @@ __global__ __launch_bounds__(256, 1) void flat_scan16_kernel(const ScanArgs a) {
     }
     if (a.timeline) ++dbg_iter;
     __builtin_amdgcn_s_barrier();
-#if RR_SCAN_STAGGER
-    // the four waves leave the barrier together and share one address unit: start wave w one MFMA time (16 cycles) x w late so
-    // that their DMA instructions, which sit at the same places of the same code, do not arrive there together
-    if (wave & 1) asm volatile("s_nop 15" ::: "memory");
-    if (wave & 2) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-#endif
     int nslot = slot + INFL;
     if (nslot >= NS) nslot -= NS;
     uint32_t j2 = j + INFL * stride;
@@ -505,50 +496,31 @@ static hipError_t launch_scan_half_resident(const ScanArgs& a, int D, bool dense
   }
 }
 
-int g_wide_min_queries = 129;  // 768 < D <= 1536: batches of at least this many queries take the wide-row kernel in one pass (RR_WIDE_MIN_QUERIES)
-int g_scan_variant = 16;       // 16 = default; 15 = the same kernel without non-temporal DMA; other values: development kernels (RR_DEV_VARIANTS builds)
-int g_generic_tall = 16;       // 16 = flat_scan_wide_kernel; 8 / 4 / 0: compiler-scheduled wide-row forms (RR_DEV_VARIANTS builds)
-
-static void read_variant_env() {
-  static const bool env_read = [] {
-    if (const char* v = tuning_env("RR_SCAN_VARIANT")) g_scan_variant = atoi(v);
-    if (const char* v = tuning_env("RR_GENERIC_TALL")) g_generic_tall = atoi(v);
-    if (const char* v = tuning_env("RR_WIDE_MIN_QUERIES")) g_wide_min_queries = atoi(v);
-#ifndef RR_DEV_VARIANTS
-    if (g_scan_variant != 15) g_scan_variant = 16;  // the development kernels are not in this build
-    g_generic_tall = 16;
-#endif
-    return true;
-  }();
-  (void)env_read;
+// 768 < D <= 1536: batches of at least this many queries take the wide-row kernel in one pass (RR_WIDE_MIN_QUERIES)
+static int wide_min_queries() {
+  static const int v = [] { const char* e = tuning_env("RR_WIDE_MIN_QUERIES"); return e ? atoi(e) : 129; }();
+  return v;
 }
 
 static bool half_resident_dim(int D) { return D == 896 || D == 1024 || D == 1280 || D == 1536; }
 // queries one scan launch serves: 256, or 128 where only 32 queries per wave stay resident (768 < D <= 1536) and the batch is small
 int scan_queries_per_launch(int D, int nq) {
-  read_variant_env();
-  if (g_scan_variant == 3) return 256;
-  return (half_resident_dim(D) && nq < g_wide_min_queries) ? 128 : 256;  // (an L2 search at these dims still works in 128-query blocks: each goes to the wide-row kernel)
+  return (half_resident_dim(D) && nq < wide_min_queries()) ? 128 : 256;  // (an L2 search at these dims still works in 128-query blocks: each goes to the wide-row kernel)
 }
 
 // 16-query blocks each wave keeps resident in the kernel that will serve (D, nq, metric): 4 (d <= 768), 2 (768 < d <= 1536 and a
-// small inner-product batch), 0 = the wide-row kernels, which stream the row-major queries.  The prep kernel lays the queries out
-// accordingly (fragment order).
+// small inner-product batch), 4 = the wide-row kernels (they stream the queries, from the same layout).  The prep kernel lays the
+// queries out accordingly (fragment order).
 int scan_query_blocks_per_wave(int D, int nq, bool l2) {
-  read_variant_env();
   if (D <= kMaxResidentDim) return 4;
-  if (half_resident_dim(D) && nq < g_wide_min_queries && !l2) return 2;
-  return RR_WIDE_QFRAG ? 4 : 0;   // wide-row kernels: the 16 blocks of a 256-query pass, same [block][k slice][lane][8] order
+  if (half_resident_dim(D) && nq < wide_min_queries() && !l2) return 2;
+  return 4;   // wide-row kernels: the 16 blocks of a 256-query pass, same [block][k slice][lane][8] order
 }
 
 // candidate buffers per (workgroup, query) of the kernel that will serve this block: 4 lane quarters; the row-split wide-row
 // kernel 8 (two waves share each query)
 int scan_bufs_per_wg(int D, int nq, bool l2, int k) {
-  read_variant_env();
-#ifdef RR_DEV_VARIANTS
-  if (!l2 && dev_scan_bufs_per_wg(D, g_scan_variant, g_generic_tall) != 4) return dev_scan_bufs_per_wg(D, g_scan_variant, g_generic_tall);
-#endif
-  if (half_resident_dim(D) && nq < g_wide_min_queries && !l2) return 4;
+  if (half_resident_dim(D) && nq < wide_min_queries() && !l2) return 4;
   return scan_wide_rowsplit(D, nq, l2, k) ? 8 : 4;
 }
 
@@ -563,7 +535,7 @@ static hipError_t launch_scan16(const ScanArgs& a, int grid, hipStream_t st) {
 
 template <typename T, int D>
 static hipError_t launch_scan_t(const ScanArgs& a, bool dense, int grid, hipStream_t st) {
-  const bool nt = (size_t)a.n_rows * D * 2 > kNtThresholdBytes && g_scan_variant != 15;
+  const bool nt = (size_t)a.n_rows * D * 2 > kNtThresholdBytes;
   if (a.ranges) {       // chunk launch of a segmented search (inner product, filter launches only)
     if (a.half_sqnorm || dense) return hipErrorNotSupported;
     return nt ? launch_scan16<T, D, false, true, false, true>(a, grid, st) : launch_scan16<T, D, false, false, false, true>(a, grid, st);
@@ -604,17 +576,10 @@ static hipError_t launch_scan_i8(const ScanArgs& a, int D, bool dense, int grid,
 }
 
 hipError_t launch_flat_scan(const ScanArgs& a, int dtype, int D, bool dense, int grid, hipStream_t st) {
-  read_variant_env();
   if (dtype == kDtypeI8) return a.half_sqnorm ? hipErrorNotSupported : launch_scan_i8(a, D, dense, grid, st);
   if (dtype != RR_DTYPE_F16 && dtype != RR_DTYPE_BF16) return hipErrorInvalidValue;
-#ifdef RR_DEV_VARIANTS
-  if (dev_scan_handles(a, D, g_scan_variant, g_generic_tall)) {
-    if (a.ranges) return hipErrorNotSupported;   // the development kernels have no tile cursor: plain searches only
-    return launch_dev_scan(a, dtype, D, dense, grid, st, g_scan_variant, g_generic_tall);
-  }
-#endif
   const bool f16 = dtype == RR_DTYPE_F16;
-  if (half_resident_dim(D) && (int)a.nq < g_wide_min_queries && !a.half_sqnorm)  // 768 < D <= 1536, small batch: 32 resident queries per wave
+  if (half_resident_dim(D) && (int)a.nq < wide_min_queries() && !a.half_sqnorm)  // 768 < D <= 1536, small batch: 32 resident queries per wave
     return f16 ? launch_scan_half_resident<_Float16>(a, D, dense, grid, st) : launch_scan_half_resident<__bf16>(a, D, dense, grid, st);
   if (D > kMaxResidentDim)  // wide rows (flat_scan_wide.hip); at 768 < D <= 1536 one pass of it beats two passes of the half-resident kernel
     return launch_scan_wide(a, dtype, D, dense, grid, st);
@@ -623,8 +588,7 @@ hipError_t launch_flat_scan(const ScanArgs& a, int dtype, int D, bool dense, int
 
 // the kernel launch_flat_scan dispatches a filter launch of (D, nq queries in the block) to
 const char* scan_kernel_name(int D, int nq, bool l2) {
-  read_variant_env();
-  if (half_resident_dim(D) && nq < g_wide_min_queries && !l2) return "flat_scan16h_kernel";
+  if (half_resident_dim(D) && nq < wide_min_queries() && !l2) return "flat_scan16h_kernel";
   if (D > kMaxResidentDim) return scan_wide_kernel_name(D, nq);
   return "flat_scan16_kernel";
 }

@@ -1,5 +1,5 @@
-// Device helpers shared by the scan kernels (flat_scan.hip: production kernels; flat_scan_dev.hip: measured alternatives
-// kept for A/B runs): MFMA wrappers, asm LDS / wait primitives, the exact wave-level compaction and the tile epilogues.
+// Device helpers shared by the scan kernels (flat_scan.hip, flat_scan_wide.hip): MFMA wrappers, asm LDS / wait primitives, the
+// exact wave-level compaction, the tile cursor of segmented searches and the tile epilogue.
 #pragma once
 #include <stdlib.h>
 
@@ -12,19 +12,9 @@
 namespace rr {
 
 
-template <typename T> struct Mfma;
-template <> struct Mfma<_Float16> {
-  typedef f16x8 frag;
-  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct Mfma<__bf16> {
-  typedef bf16x8 frag;
-  static __device__ __forceinline__ f32x16 run(frag a, frag b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
+template <typename T> struct Mfma;   // the 16-byte MFMA operand fragment of an element type
+template <> struct Mfma<_Float16> { typedef f16x8 frag; };
+template <> struct Mfma<__bf16> { typedef bf16x8 frag; };
 
 // int8 screening copy (rr_flat_search_screened): rows are viewed as pairs of bytes, so a row of D "elements" is 2*D
 // int8 values and every address computation below is the f16 one; only the MFMA opcode (K = 64 bytes per 16-byte lane
@@ -32,33 +22,6 @@ template <> struct Mfma<__bf16> {
 struct I8Pair { int16_t v; };
 template <> struct Mfma<I8Pair> { typedef s16x8 frag; };
 
-// Inline-asm MFMA: accumulator in VGPRs (the epilogue's VALU reads it there), corpus fragment (A) in VGPRs, query fragment (B) either in AGPRs
-// (block 0) or VGPRs (block 1).  hipcc otherwise keeps part of the resident queries in AGPRs and copies
-// them to VGPRs with v_accvgpr_read before every MFMA (~250 copies per tile).  The accumulate chain
-// (srcC == vDst) needs no wait states; the reader after the chain is fenced by mfma_drain().
-template <typename T> struct MfmaAsm;
-template <> struct MfmaAsm<_Float16> {
-  static __device__ __forceinline__ void first_a(f32x16& c, f16x8 a, f16x8 b) {
-    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=v"(c) : "v"(a), "a"(b));
-  }
-  static __device__ __forceinline__ void acc_a(f32x16& c, f16x8 a, f16x8 b) {
-    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "a"(b));
-  }
-  static __device__ __forceinline__ void acc_v(f32x16& c, f16x8 a, f16x8 b) {
-    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-  }
-};
-template <> struct MfmaAsm<__bf16> {
-  static __device__ __forceinline__ void first_a(f32x16& c, bf16x8 a, bf16x8 b) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=v"(c) : "v"(a), "a"(b));
-  }
-  static __device__ __forceinline__ void acc_a(f32x16& c, bf16x8 a, bf16x8 b) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "a"(b));
-  }
-  static __device__ __forceinline__ void acc_v(f32x16& c, bf16x8 a, bf16x8 b) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-  }
-};
 // Global load of one fragment directly into accumulator registers (gfx90a+ VMEM may target AGPRs).
 template <typename F, typename P>
 __device__ __forceinline__ void agpr_load_frag(F& dst, const P* ptr) {
@@ -75,19 +38,6 @@ template <int N>
 __device__ __forceinline__ void lgkm_wait() {
   asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N));
 }
-// Diagnostic build only (VARIANT 2): shader-clock stamp, fenced so the segment it closes is complete.
-__device__ __forceinline__ uint64_t stamp() {
-  uint64_t t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-// 8-pass XDL result -> any non-MFMA reader needs 18 wait states the compiler cannot see inside asm.
-__device__ __forceinline__ void mfma_drain(f32x16& a0, f32x16& a1) {
-  asm volatile("s_nop 15\n\ts_nop 7" : "+v"(a0), "+v"(a1));
-}
-
 // Wave-cooperative exact compaction of one lane's candidate buffer: keep the k largest keys
 // (sorted, descending) and return the k-th key.  All 64 lanes participate; buf/scratch/cnt are
 // wave-uniform.  Keys are unique (ids are unique), so ranks form a permutation.
@@ -124,92 +74,12 @@ __device__ __forceinline__ float max4(float a, float b, float c, float d) {
   return r;
 }
 
-// Per-lane filter state: strict thresholds, candidate counts and buffer offsets of the lane's two queries.
-struct LaneState {
-  float thr0, thr1;
-  uint32_t cnt0, cnt1, off0, off1;
-};
-
-// Epilogue of one 32-row tile: a0/a1 hold the lane's 16 corpus rows (m = (i&3) + 8*(i>>2) + 4h) for its query of
-// block 0 / block 1.  DENSE: store every score.  Otherwise: strict-threshold filter, append survivors as order keys
-// to the lane's private buffers, compact exactly when a buffer is nearly full.
-template <bool DENSE>
-__device__ __forceinline__ void tile_epilogue(const ScanArgs& a, LaneState& st, const f32x16& a0, const f32x16& a1, uint32_t j,
-                                              uint32_t q0i, uint32_t q1i, int h, int lane, int wave) {
-    const uint32_t tile = a.tile_first + j * a.tile_stride;
-    if (DENSE) {
-      // column = j*32 + m, m = (i&3) + 8*(i>>2) + 4h
-      float* d0 = a.dense + (size_t)q0i * a.dense_ld + j * kTileRows + 4 * h;
-      float* d1 = a.dense + (size_t)q1i * a.dense_ld + j * kTileRows + 4 * h;
-#pragma unroll
-      for (int i4 = 0; i4 < 4; ++i4) {
-        *(f32x4*)(d0 + 8 * i4) = f32x4{a0[4 * i4], a0[4 * i4 + 1], a0[4 * i4 + 2], a0[4 * i4 + 3]};
-        *(f32x4*)(d1 + 8 * i4) = f32x4{a1[4 * i4], a1[4 * i4 + 1], a1[4 * i4 + 2], a1[4 * i4 + 3]};
-      }
-    } else {
-      // two-level test: maxima of the four 4-register groups (rows 8g+4h .. +3), then their maximum
-      float g0[4], g1[4];
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        g0[g] = max4(a0[4 * g], a0[4 * g + 1], a0[4 * g + 2], a0[4 * g + 3]);
-        g1[g] = max4(a1[4 * g], a1[4 * g + 1], a1[4 * g + 2], a1[4 * g + 3]);
-      }
-      const float m0 = max4(g0[0], g0[1], g0[2], g0[3]);
-      const float m1 = max4(g1[0], g1[1], g1[2], g1[3]);
-      if (__builtin_amdgcn_ballot_w64(m0 > st.thr0 || m1 > st.thr1)) {
-        // rare: a typical hit is ONE lane with ONE score, so only the group that holds it is expanded
-        const uint32_t row0 = tile * kTileRows + 4 * h;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          if (__builtin_amdgcn_ballot_w64(g0[g] > st.thr0)) {
-#pragma unroll
-            for (int i = 4 * g; i < 4 * g + 4; ++i) {
-              const uint32_t id = row0 + (i & 3) + 8 * (i >> 2);
-              if (a0[i] > st.thr0 && id < a.n_rows) {
-                a.cand[(size_t)st.off0 + st.cnt0] = make_key(a0[i], id);
-                ++st.cnt0;
-              }
-            }
-          }
-          if (__builtin_amdgcn_ballot_w64(g1[g] > st.thr1)) {
-#pragma unroll
-            for (int i = 4 * g; i < 4 * g + 4; ++i) {
-              const uint32_t id = row0 + (i & 3) + 8 * (i >> 2);
-              if (a1[i] > st.thr1 && id < a.n_rows) {
-                a.cand[(size_t)st.off1 + st.cnt1] = make_key(a1[i], id);
-                ++st.cnt1;
-              }
-            }
-          }
-        }
-        // keep >= 16 free slots per buffer; compaction is exact and raises the lane threshold
-        const uint32_t lim = (uint32_t)a.cap - 16u;
-        if (__builtin_amdgcn_ballot_w64(st.cnt0 > lim || st.cnt1 > lim)) {
-          uint64_t* scratch = a.scratch + (size_t)(blockIdx.x * 4 + wave) * a.cap;
-#pragma unroll 1
-          for (int b = 0; b < 2; ++b) {
-            uint64_t mask = __builtin_amdgcn_ballot_w64((b ? st.cnt1 : st.cnt0) > lim);
-            while (mask) {
-              const int L = __builtin_ctzll(mask);
-              mask &= mask - 1;
-              const uint32_t off = __shfl(b ? st.off1 : st.off0, L, 64);
-              const int cnt = (int)__shfl(b ? st.cnt1 : st.cnt0, L, 64);
-              const uint64_t kth = wave_compact(a.cand + (size_t)__builtin_amdgcn_readfirstlane(off), scratch,
-                                                __builtin_amdgcn_readfirstlane(cnt), a.k, lane);
-              if (lane == L) {
-                if (b) { st.cnt1 = a.k; st.thr1 = key_score(kth); }
-                else   { st.cnt0 = a.k; st.thr0 = key_score(kth); }
-              }
-            }
-          }
-        }
-      }
-    }
-}
-
-// 16x16x32 MFMA shape.  Same design, registers and LDS image as flat_scan_kernel; the chip holds a higher clock on
-// this shape under the combined HBM + MFMA load (measured: -6.7 % time at equal flops and operands), which is what
-// bounds the kernel.  Per wave: 4 query blocks of 16 (B operand) x 2 row blocks of 16 (A operand); D fragment:
+// 16x16x32 MFMA shape (the chip holds a higher clock on it under the combined HBM + MFMA load than on 32x32x16: measured
+// -6.7 % time at equal flops and operands, which is what bounds the kernel).  Inline asm: accumulator in VGPRs (the epilogue's
+// VALU reads it there), corpus fragment (A) in VGPRs, query fragment (B) in AGPRs or VGPRs; hipcc otherwise keeps part of the
+// resident queries in AGPRs and copies them to VGPRs with v_accvgpr_read before every MFMA.  The accumulate chain (srcC == vDst)
+// needs no wait states; the reader after the chain is fenced by the caller (s_nop).
+// Per wave: 4 query blocks of 16 (B operand) x 2 row blocks of 16 (A operand); D fragment:
 // column = lane&15 -> query, rows 4*(lane>>4) + reg.  A lane therefore owns 4 queries x 8 rows per tile, and the
 // candidate buffers are per (workgroup, query, lane quarter): 4 per workgroup and query.
 template <typename T> struct Mfma16Asm;
@@ -240,26 +110,11 @@ __host__ __device__ constexpr int scan16_slots(int D) { return D >= 640 ? 3 : D 
 
 // LDS reads hidden from hipcc: next to LDS-DMA it answers every LDS load it can see with s_waitcnt vmcnt(0), which drains
 // the DMA ring of the scan kernels.  Each statement waits for its own data (the fragment ring is empty wherever these are used).
-__device__ __forceinline__ float lds_load_f32(uint32_t byte_addr) {
-  float v;
-  asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(byte_addr) : "memory");
-  return v;
-}
 __device__ __forceinline__ f32x4 lds_load_f32x4(uint32_t byte_addr) {
   f32x4 v;
   asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(byte_addr) : "memory");
   return v;
 }
-
-// Loads of the rare paths, with their own wait and invisible to hipcc's waitcnt pass: a VMEM load it can see inside a loop that
-// keeps LDS-DMA / prefetched registers in flight makes it put s_waitcnt vmcnt(0) into the hot path (pitfall i).
-// The wait drains the wave's DMA ring too, which is always safe (the counted waits that follow are then met at once).
-__device__ __forceinline__ uint32_t asm_load_u32(const void* p) {
-  uint32_t v;
-  asm volatile("global_load_dword %0, %1, off\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
-  return v;
-}
-__device__ __forceinline__ float asm_load_f32(const void* p) { return __uint_as_float(asm_load_u32(p)); }
 
 // ---- segmented search: launch ordinal -> tile --------------------------------------------------------------------------------
 // A chunk launch of a segmented search covers one run of tiles per segment (ScanArgs::ranges).  A workgroup's ordinals only move
@@ -363,20 +218,6 @@ __device__ __forceinline__ void tile_epilogue16(const ScanArgs& a, LaneState4& s
     load_thresholds<NQB>(a, e.seg, qi, st.thr);
   }
   const uint32_t tile = a.tile_first + j * a.tile_stride + (SEG ? (uint32_t)st.cur.delta : 0u);
-#ifndef RR_EPILOGUE_MASKS
-#define RR_EPILOGUE_MASKS 0   // 1: the insertion path branches on wave masks made by the filter instead of re-deriving them per group (measured: headline -0.4 %, config 2 +0.8 %, i.e. noise; off)
-#endif
-#if RR_EPILOGUE_MASKS
-  uint64_t hm[2][4];          // lanes whose 4-row group of (row block, query block) holds a score above the lane's threshold
-  uint64_t any = 0;
-#pragma unroll
-  for (int qb = 0; qb < NQB; ++qb) {
-    hm[0][qb] = __builtin_amdgcn_ballot_w64(max4v(acc[0][qb]) > st.thr[qb]);
-    hm[1][qb] = __builtin_amdgcn_ballot_w64(max4v(acc[1][qb]) > st.thr[qb]);
-    any |= hm[0][qb] | hm[1][qb];
-  }
-  if (!any) return;
-#else
   float gm[2][4];
   bool hit = false;
 #pragma unroll
@@ -386,18 +227,13 @@ __device__ __forceinline__ void tile_epilogue16(const ScanArgs& a, LaneState4& s
     hit = hit || (gm[0][qb] > st.thr[qb]) || (gm[1][qb] > st.thr[qb]);
   }
   if (!__builtin_amdgcn_ballot_w64(hit)) return;
-#endif
   // rare: typically ONE lane with ONE score; only the 4-row group that holds it is expanded
   const uint32_t row0 = tile * kTileRows + 4 * g;
 #pragma unroll
   for (int qb = 0; qb < NQB; ++qb) {
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb) {
-#if RR_EPILOGUE_MASKS
-      if (hm[rb][qb]) {
-#else
       if (__builtin_amdgcn_ballot_w64(gm[rb][qb] > st.thr[qb])) {
-#endif
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const uint32_t id = row0 + rb * 16 + i;
@@ -446,16 +282,8 @@ __device__ __forceinline__ void static_for(F&& f) { static_for_impl(std::make_in
 constexpr size_t kNtThresholdBytes = 256ull << 20;
 
 // flat_scan_wide.hip
-#ifndef RR_WIDE_QFRAG
-#define RR_WIDE_QFRAG 1   // the pd / wide8 kernels' query loads read prep_kernel's fragment-order copy (one contiguous KiB per
-#endif                    // instruction) instead of 16 rows x 64 B of the row-major block; 0 = row-major (A/B builds)
 hipError_t launch_scan_wide(const ScanArgs& a, int dtype, int D, bool dense, int grid, hipStream_t st);
 const char* scan_wide_kernel_name(int D, int nq);
 bool scan_wide_rowsplit(int D, int nq, bool l2, int k);   // the row-split kernel serves this launch (8 candidate buffers per workgroup and query)
-
-// flat_scan_dev.hip (only in builds with -DRR_DEV_VARIANTS): the development kernels behind RR_SCAN_VARIANT / RR_GENERIC_TALL
-bool dev_scan_handles(const ScanArgs& a, int D, int variant, int tall);
-int dev_scan_bufs_per_wg(int D, int variant, int tall);
-hipError_t launch_dev_scan(const ScanArgs& a, int dtype, int D, bool dense, int grid, hipStream_t st, int variant, int tall);
 
 }  // namespace rr

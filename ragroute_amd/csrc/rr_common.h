@@ -6,7 +6,7 @@
 
 namespace rr {
 
-// Tuning / diagnostic variables (RR_SCAN_VARIANT, RR_WIDE_*, RR_CHUNK_GROWTH, RR_SAMPLE_ROWS, RR_SCAN_TIMELINE, ...) re-route kernels
+// Tuning / diagnostic variables (RR_WIDE_*, RR_CHUNK_GROWTH, RR_SAMPLE_ROWS, RR_SCAN_TIMELINE, ...) re-route kernels
 // and schedules.  Only development builds (-DRR_DEV_VARIANTS, ragroute_amd/_build.py) honour them: a PRODUCT build reads none, so
 // a stray variable in a service's environment cannot change the kernel under test or in production
 // (tests/test_cabi_exports.py::test_product_library_ignores_tuning_variables).
@@ -22,7 +22,6 @@ inline const char* tuning_env(const char* name) {
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kQueriesPerBlock = 256;  // one scan launch serves 256 queries (4 waves x 64)

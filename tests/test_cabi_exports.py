@@ -66,8 +66,9 @@ def test_segment_row_counts_cannot_overflow():
 
 
 def test_product_library_ignores_tuning_variables():
-    """RR_WIDE_* / RR_SCAN_VARIANT / RR_CHUNK_GROWTH re-route kernels and schedules in DEVELOPMENT builds only (rr::tuning_env):
-    with every one of them set, a product library names the same kernels as without."""
+    """RR_WIDE_* / RR_CHUNK_GROWTH / ... re-route kernels and schedules in DEVELOPMENT builds only (rr::tuning_env): with every one
+    of them set - and the names that older scripts may still export: RR_WIDE_PD, RR_SCAN_VARIANT, RR_GENERIC_TALL - a product
+    library names the same kernels as without."""
     import subprocess
     import sys
     code = ("import sys; sys.path.insert(0, %r)\nfrom ragroute_amd import _lib\nL = _lib.lib()\n"
@@ -80,13 +81,15 @@ def test_product_library_ignores_tuning_variables():
     assert plain.returncode == 0 and other.returncode == 0, (plain.stderr[-500:], other.stderr[-500:])
     assert plain.stdout == other.stdout and "flat_scan_wide_rs_kernel" in plain.stdout
     src = "".join(open(os.path.join(ROOT, "ragroute_amd", "csrc", f)).read() for f in os.listdir(os.path.join(ROOT, "ragroute_amd", "csrc"))
-                  if f.endswith((".hip", ".h")) and f != "flat_scan_dev.hip")
+                  if f.endswith((".hip", ".h")))
     assert len(re.findall(r"\bgetenv\(", src)) == 1, "every RR_* variable goes through rr::tuning_env (rr_common.h)"
+    retired = re.findall(r"\b(?:flat_scan_wide_kernel|flat_scan_kernel|flat_scan16x8_kernel|flat_scan_generic_kernel|flat_scan_tall_kernel)\b", src)
+    assert not retired, "the development kernels and the round-1 wide-row kernel were removed (DESIGN_HISTORY.md): %s" % sorted(set(retired))
 
 
 def test_library_under_test_is_a_product_build():
-    """rr_build_flags(): no -D switch, i.e. neither the development kernels nor the timing-only ablations (which produce wrong
-    scores) are compiled in; RR_LIB_OVERRIDE (A/B libraries) must not be set when the suite runs."""
+    """rr_build_flags(): no -D switch, i.e. not a development build that honours the tuning variables; RR_LIB_OVERRIDE (A/B
+    libraries) must not be set when the suite runs."""
     from ragroute_amd import _build, _lib
     assert not os.environ.get("RR_LIB_OVERRIDE")
     flags = _lib.lib().rr_build_flags().decode()

@@ -20,8 +20,6 @@
 #   service [ROWS WINDOWS...]   tools/service_bench.py
 #   fuzz SEED COUNT [segments|big]   tools/fuzz_parity.py
 #   probe CYCLES          tools/remap_probe.py (stale-input root-cause probe)
-#   rswiden               the row-split kernel's widened dispatch against round 3's limits (development library _dev, one leg per old limit;
-#                         profiles/r04/rowsplit_widening.json)
 #   config2               config 2: bootstrap sample size A/B (development library) + per-search kernel timeline (tools/trace_gaps.py;
 #                         profiles/r04/config2_floor.json)
 # variables: OUT, SHAPES ("rows dim;rows dim ..."), K, ITERS, BATCH, REPS, ENVS, STEPS
@@ -128,12 +126,6 @@ service)
   timeout -k 10 700 python tools/service_bench.py "$@" > $O/service.json 2> $O/service.err; grep -v amdgpu.ids $O/service.err | cut -c1-330 ;;
 fuzz)
   timeout -k 10 1000 python tools/fuzz_parity.py "$@" > $O/fuzz_$(echo "$@" | tr ' ' '_').log 2>&1; rc=$?; tail -1 $O/fuzz_$(echo "$@" | tr ' ' '_').log | cut -c1-300; exit $rc ;;
-rswiden)
-  OUT=$O_BASE/rs_k300 SHAPES="2000000 2048" K=300 ITERS=20 ENVS="RR_WIDE_RS_MAXK=128;RR_WIDE_RS_MAXK=1024" bash tools/collect.sh ab _dev
-  OUT=$O_BASE/rs_l2 SHAPES="4000000 1024;2000000 4096" K=10 METRIC=l2 ITERS=20 ENVS="RR_WIDE_RS_L2=0;RR_WIDE_RS_L2=1" bash tools/collect.sh ab _dev
-  for q in 193 200 208; do
-    OUT=$O_BASE/rs_q$q SHAPES="4000000 1024;2000000 2048;2000000 4096" K=10 BATCH=$q ITERS=20 ENVS="RR_WIDE_RS_MINQ=209;RR_WIDE_RS_MINQ=193" bash tools/collect.sh ab _dev
-  done ;;
 config2)
   OUT=$O_BASE/c2_sample SHAPES="1000000 768" K=32 ITERS=50 REPS=3 ENVS="RR_SAMPLE_ROWS=8192;RR_SAMPLE_ROWS=4096;RR_SAMPLE_ROWS=2048" bash tools/collect.sh ab _dev
   (cd /tmp && rocprofv3 --kernel-trace -d $R/$O/trace -o t --output-format csv -- python3 $R/tools/shape_bench.py 1000000 768 256 32 fp16 30 > $R/$O/shape.json 2> $R/$O/trace.err)
