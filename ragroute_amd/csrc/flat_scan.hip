@@ -7,8 +7,8 @@
 //    MFMA B-operand fragments (D=768 -> 384 of its 512 VGPR/AGPRs).  4 waves x 64 = 256.
 //  * The corpus is streamed exactly once, HBM -> LDS by LDS-DMA (global_load_lds_dwordx4) in
 //    32-row tiles through a 3-slot ring (2 tiles in flight per CU); every 1 KiB DMA piece is
-//    8 rows x 128 contiguous bytes (whole cache lines), XOR-swizzled on the SOURCE side so the
-//    later ds_read_b128 of MFMA A-fragments is bank-conflict-free.
+//    8 rows x 128 contiguous bytes (whole cache lines) of the swizzled LDS image that flat_scan_common.h
+//    defines ("LDS image of a k-group block").
 //  * Per tile: 48 x { ds_read_b128 corpus fragment ; 4 x v_mfma_f32_16x16x32 } with the corpus as A and the queries
 //    as B, so every lane ends up owning ONE query (column) and a few corpus rows per result block: the top-k filter
 //    is a per-lane compare against that query's threshold, no cross-lane work.  No inter-workgroup reuse exists
@@ -58,19 +58,11 @@ __global__ __launch_bounds__(256, 1) void flat_scan16_kernel(const ScanArgs a) {
   // ---- LDS image.  A fragment (rb, s2): row rb*16 + col, chunk 4*(s2&1) + g of
   // k group s2>>1 -------------------------------------------------------------------------------------------------
   uint32_t roff[2][2];
-  {
-    const int rho = col & 7;
 #pragma unroll
-    for (int rb = 0; rb < 2; ++rb) {
-      const int p = 2 * rb + (col >> 3);
-      const int f = ((rho >> 1) & 3) | ((p & 1) << 2);
+  for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
-      for (int par = 0; par < 2; ++par) roff[rb][par] = p * 1024 + rho * 128 + (((4 * par + g) ^ f) * 16);
-    }
-  }
-  const int rho_w = lane >> 3, sig = lane & 7;
-  const int f_w = ((rho_w >> 1) & 3) | ((wave & 1) << 2);
-  const int c_w = sig ^ f_w;
+    for (int par = 0; par < 2; ++par) roff[rb][par] = kgroup_frag_offset(2 * rb + (col >> 3), col & 7, par, g);
+  const int rho_w = lane >> 3, c_w = kgroup_dma_chunk(lane, wave & 1);   // DMA: wave w fills row group w of the tile
   TileCursor dcur;   // the DMA stream's position in the launch's tile runs (segmented search; plain: tile_first + j * tile_stride)
   if (SEG) cursor_init(a, dcur);
   auto tile_src = [&](uint32_t j) -> const char* {
@@ -187,14 +179,7 @@ __global__ __launch_bounds__(256, 1) void flat_scan16_kernel(const ScanArgs a) {
 #pragma unroll
       for (int f = 0; f < NF; ++f) {
         const int s2 = f >> 1, rb = f & 1;
-        if (NF - f >= NB) lgkm_wait<NB - 1>();
-        else if (NF - f == 7) lgkm_wait<6>();
-        else if (NF - f == 6) lgkm_wait<5>();
-        else if (NF - f == 5) lgkm_wait<4>();
-        else if (NF - f == 4) lgkm_wait<3>();
-        else if (NF - f == 3) lgkm_wait<2>();
-        else if (NF - f == 2) lgkm_wait<1>();
-        else lgkm_wait<0>();
+        lgkm_wait_left<NB>(NF - f);
 #pragma unroll
         for (int qb = 0; qb < NQB; ++qb) {
           const bool in_a = qb * KS2 + s2 < NAQ;
@@ -321,17 +306,11 @@ __global__ __launch_bounds__(256, 1) void flat_scan16h_kernel(const ScanArgs a) 
   // A fragment of slice s2 in a 16-row unit: row col (row group p = col>>3), chunk 4*(s2&1) + g of k group s2>>1;
   // unit image: piece (kg, p) at (kg*2 + p) * 1024
   uint32_t roff[2];
-  {
-    const int p = col >> 3, rho = col & 7;
-    const int f = ((rho >> 1) & 3) | (p << 2);
 #pragma unroll
-    for (int par = 0; par < 2; ++par) roff[par] = p * 1024 + rho * 128 + (((4 * par + g) ^ f) * 16);
-  }
+  for (int par = 0; par < 2; ++par) roff[par] = kgroup_frag_offset(col >> 3, col & 7, par, g);
   // DMA: wave w fills row group p = w&1 of the k groups with parity w>>1
   const int pw = wave & 1, kpar = wave >> 1;
-  const int rho_w = lane >> 3, sig = lane & 7;
-  const int f_w = ((rho_w >> 1) & 3) | (pw << 2);
-  const int c_w = sig ^ f_w;
+  const int rho_w = lane >> 3, c_w = kgroup_dma_chunk(lane, pw);
   // unit ordinal u = 2*i + half, i-th tile of this workgroup (tile ordinal j = blockIdx + i*gridDim)
   const uint32_t my_tiles = a.n_tiles > blockIdx.x ? (a.n_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;
   const uint32_t n_units = 2 * my_tiles;
@@ -383,14 +362,7 @@ __global__ __launch_bounds__(256, 1) void flat_scan16h_kernel(const ScanArgs a) 
       for (int f = 0; f < NB; ++f) lds_read_frag(c[f], ab[f & 1], (f >> 1) * 2048);
 #pragma unroll
       for (int f = 0; f < KS2; ++f) {
-        if (KS2 - f >= NB) lgkm_wait<NB - 1>();
-        else if (KS2 - f == 7) lgkm_wait<6>();
-        else if (KS2 - f == 6) lgkm_wait<5>();
-        else if (KS2 - f == 5) lgkm_wait<4>();
-        else if (KS2 - f == 4) lgkm_wait<3>();
-        else if (KS2 - f == 3) lgkm_wait<2>();
-        else if (KS2 - f == 2) lgkm_wait<1>();
-        else lgkm_wait<0>();
+        lgkm_wait_left<NB>(KS2 - f);
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
           const bool in_a = qb * KS2 + f < NAQ;
@@ -473,16 +445,9 @@ static hipError_t launch_scan16h(const ScanArgs& a, bool dense, int grid, hipStr
   constexpr int nslot = (160 * 1024) / unit >= 4 ? 4 : 3;
   const size_t lds = (size_t)nslot * unit;
   const bool nt = !dense && (size_t)a.n_rows * D * 2 > (256ull << 20);
-  hipError_t e;
-#define RR_LAUNCH_H(DENSE_, NT_)                                                                                      \
-  e = hipFuncSetAttribute((const void*)flat_scan16h_kernel<T, D, DENSE_, NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-  if (e != hipSuccess) return e;                                                                                      \
-  hipLaunchKernelGGL((flat_scan16h_kernel<T, D, DENSE_, NT_>), dim3(grid), dim3(256), lds, st, a);
-  if (dense) { RR_LAUNCH_H(true, false) }
-  else if (nt) { RR_LAUNCH_H(false, true) }
-  else { RR_LAUNCH_H(false, false) }
-#undef RR_LAUNCH_H
-  return hipGetLastError();
+  if (dense) return launch_with_lds(flat_scan16h_kernel<T, D, true, false>, grid, 256, lds, st, a);
+  if (nt) return launch_with_lds(flat_scan16h_kernel<T, D, false, true>, grid, 256, lds, st, a);
+  return launch_with_lds(flat_scan16h_kernel<T, D, false, false>, grid, 256, lds, st, a);
 }
 
 template <typename T>
@@ -527,10 +492,7 @@ int scan_bufs_per_wg(int D, int nq, bool l2, int k) {
 template <typename T, int D, bool DENSE, bool NT = false, bool L2 = false, bool SEG = false>
 static hipError_t launch_scan16(const ScanArgs& a, int grid, hipStream_t st) {
   const size_t lds = scan16_slots(D) * ((size_t)kTileRows * D * 2 + 256);  // ring + L2 norm slots
-  hipError_t e = hipFuncSetAttribute((const void*)flat_scan16_kernel<T, D, DENSE, NT, L2, SEG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((flat_scan16_kernel<T, D, DENSE, NT, L2, SEG>), dim3(grid), dim3(256), lds, st, a);
-  return hipGetLastError();
+  return launch_with_lds(flat_scan16_kernel<T, D, DENSE, NT, L2, SEG>, grid, 256, lds, st, a);
 }
 
 template <typename T, int D>

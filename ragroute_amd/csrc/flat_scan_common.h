@@ -22,6 +22,11 @@ template <> struct Mfma<__bf16> { typedef bf16x8 frag; };
 struct I8Pair { int16_t v; };
 template <> struct Mfma<I8Pair> { typedef s16x8 frag; };
 
+template <int... Is, typename F>
+__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, Is...>, F&& f) { (f(std::integral_constant<int, Is>{}), ...); }
+template <int N, typename F>
+__device__ __forceinline__ void static_for(F&& f) { static_for_impl(std::make_integer_sequence<int, N>{}, f); }  // body sees a constexpr index
+
 // Global load of one fragment directly into accumulator registers (gfx90a+ VMEM may target AGPRs).
 template <typename F, typename P>
 __device__ __forceinline__ void agpr_load_frag(F& dst, const P* ptr) {
@@ -37,6 +42,39 @@ __device__ __forceinline__ void lds_read_frag(F& dst, uint32_t addr, int off) {
 template <int N>
 __device__ __forceinline__ void lgkm_wait() {
   asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N));
+}
+// Ahead of consuming a fragment when LEFT fragments are not yet consumed and the ring holds NB reads: the oldest read has landed
+// once at most min(LEFT, NB) - 1 younger ones are still in flight.
+template <int LEFT, int NB>
+__device__ __forceinline__ void lgkm_wait_left() {
+  lgkm_wait<(LEFT >= NB ? NB : LEFT) - 1>();
+}
+// The same for the two `#pragma unroll` loops of flat_scan.hip, whose index is a constant by the time the wait is emitted but not
+// for the language: a chain of compares that folds to one wait.  (Those loops stay loops: written as static_for, the d = 768 and
+// the half-resident kernels, whose queries live partly in VGPRs, came out with 7 to 9 more instructions per tile.)
+template <int NB>
+__device__ __forceinline__ void lgkm_wait_left(int left) {
+  static_for<NB>([&](auto i) {
+    if ((left >= NB ? NB : left) - 1 == decltype(i)::value) lgkm_wait<decltype(i)::value>();
+  });
+}
+
+// ---- LDS image of a k-group block ------------------------------------------------------------------------------------------------
+// Every scan kernel moves the corpus HBM -> LDS in 1 KiB LDS-DMA pieces: one row group of 8 rows x one 64-wide k group = 8 x 128
+// contiguous bytes (whole cache lines), lane l of the issuing wave carrying 16 bytes of row l >> 3.  Four consecutive row groups
+// (p = 0 .. 3: a 32-row tile) of one k group form the 4 KB k-group block, row group p at p * 1024, row rho of it at + rho * 128.
+// The image is XOR-swizzled on the SOURCE side so that the later ds_read_b128 of an MFMA A fragment is bank-conflict-free: the
+// 16-byte chunk stored at position c of row rho is chunk c ^ f of that row's 128 bytes, with f = ((rho >> 1) & 3) | (parity << 2)
+// and parity = p & 1.  (A fragment read takes one chunk from each of 16 rows that lie 128 bytes apart: unswizzled, the same chunk
+// of every row falls on the same banks.  XOR is an involution, so writer and reader apply the same f.)
+__device__ __forceinline__ int kgroup_swizzle(int rho, int parity) { return ((rho >> 1) & 3) | (parity << 2); }
+// Writer: the 16-byte chunk of its source row that DMA lane `lane` fetches (it lands at position lane & 7 of row lane >> 3) for a
+// row group of the given parity.
+__device__ __forceinline__ int kgroup_dma_chunk(int lane, int parity) { return (lane & 7) ^ kgroup_swizzle(lane >> 3, parity); }
+// Reader: byte offset within the block of the A-fragment operand of the lane that owns row rho of row group p, lane quarter g:
+// chunk 4 par + g of the row (par: which 32-wide k slice of the k group).
+__device__ __forceinline__ uint32_t kgroup_frag_offset(int p, int rho, int par, int g) {
+  return p * 1024 + rho * 128 + (((4 * par + g) ^ kgroup_swizzle(rho, p & 1)) * 16);
 }
 // Wave-cooperative exact compaction of one lane's candidate buffer: keep the k largest keys
 // (sorted, descending) and return the k-th key.  All 64 lanes participate; buf/scratch/cnt are
@@ -272,14 +310,19 @@ __device__ __forceinline__ void tile_epilogue16(const ScanArgs& a, LaneState4& s
   }
 }
 
-template <int... Is, typename F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, Is...>, F&& f) { (f(std::integral_constant<int, Is>{}), ...); }
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl(std::make_integer_sequence<int, N>{}, f); }  // body sees a constexpr index
-
 // Corpora beyond the 256 MiB Infinity Cache are streamed with non-temporal LDS-DMA (read once per batch: -1.7 % at
 // B=256, -11 % for single-query searches); smaller ones keep the default policy so back-to-back searches stay on die.
 constexpr size_t kNtThresholdBytes = 256ull << 20;
+
+// Every scan kernel takes its LDS ring as dynamic shared memory above the 64 KB default: raise the kernel's limit, launch, and
+// report the launch's own error.
+template <typename K, typename... Args>
+hipError_t launch_with_lds(K kernel, int grid, int block, size_t lds, hipStream_t st, Args... args) {
+  const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, st, args...);
+  return hipGetLastError();
+}
 
 // flat_scan_wide.hip
 hipError_t launch_scan_wide(const ScanArgs& a, int dtype, int D, bool dense, int grid, hipStream_t st);

@@ -6,6 +6,13 @@
 //                             8 waves = 2 row halves x 4 query quarters, the query columns of a K step DMA'd into LDS once per CU
 //   flat_scan_wide8_kernel    d <= 2048, up to 208 queries: 8 waves, queries streamed into registers
 //   flat_scan_wide_pd_kernel  d > 2048 up to 192 queries, 9 / 11 / 12 query blocks at d <= 2048, every dense (sample) launch: 4 waves
+// What the three share is defined once, ahead of them: the fixed-AGPR accumulator access (RR_ASM_FIXED_ACC, Mfma16Fixed,
+// read_acc_fixed), the K rotation, the L2 epilogue step (subtract_half_sqnorms) and, for the pd and wide8 kernels, the query
+// prefetch discipline (pin_query_buffers, load_queries, closing_wait, dispatch_step, drain_query_buffers).  The LDS image of a
+// slab, the counted LDS wait and the launch helper come from flat_scan_common.h.  Each kernel keeps its own `step` (where its
+// loads sit inside the MFMA stream is what the kernels differ in) and its own copy of the DMA stream's addressing
+// (dma_new_group / issue_piece / dma_advance): moved into a shared struct or shared functions, in three forms, it changed the
+// hand-scheduled steps of every kernel (DESIGN_HISTORY.md, "After round 4: the scan kernels share their LDS image ...").
 #include "flat_scan_common.h"
 
 namespace rr {
@@ -17,18 +24,48 @@ namespace rr {
 // wave's queries x 128 B from L2 straight into registers a few K steps ahead (scalar base + lane offset
 // loads; every CU re-reads the query block once per 256 rows: 1 B of L2 traffic per corpus byte).
 // Per K step and wave: 32 A fragments (ring of 8 ds_read_b128) x 4 MFMA 16x16x32, 8 DMA pieces, 8 query loads.
-// The LDS image of a slab is NT copies of flat_scan16_kernel's 4 KB k-group block, so addressing is shared.
+// The LDS image of a slab is NT copies of flat_scan16_kernel's 4 KB k-group block, so the image's addressing (writer-side swizzle,
+// reader-side fragment offsets: flat_scan_common.h) is shared with it.
 // Accumulators are HARD-WIRED AGPRs a[4i .. 4i+3]: 64 tied "+a" operands (256 registers) defeat hipcc's allocator (it
 // shuttled them through scratch and v_accvgpr_mov at every loop edge).  Every statement that touches them names all 256 as
 // clobbers, so the compiler keeps nothing of its own in AGPRs and sizes the kernel's register file for them.
-#define RR_ALL_AGPRS "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", "a10", "a11", "a12", "a13", "a14", "a15", "a16", "a17", "a18", "a19", "a20", "a21", "a22", "a23", "a24", "a25", "a26", "a27", "a28", "a29", "a30", "a31", "a32", "a33", "a34", "a35", "a36", "a37", "a38", "a39", "a40", "a41", "a42", "a43", "a44", "a45", "a46", "a47", "a48", "a49", "a50", "a51", "a52", "a53", "a54", "a55", "a56", "a57", "a58", "a59", "a60", "a61", "a62", "a63", "a64", "a65", "a66", "a67", "a68", "a69", "a70", "a71", "a72", "a73", "a74", "a75", "a76", "a77", "a78", "a79", "a80", "a81", "a82", "a83", "a84", "a85", "a86", "a87", "a88", "a89", "a90", "a91", "a92", "a93", "a94", "a95", "a96", "a97", "a98", "a99", "a100", "a101", "a102", "a103", "a104", "a105", "a106", "a107", "a108", "a109", "a110", "a111", "a112", "a113", "a114", "a115", "a116", "a117", "a118", "a119", "a120", "a121", "a122", "a123", "a124", "a125", "a126", "a127", "a128", "a129", "a130", "a131", "a132", "a133", "a134", "a135", "a136", "a137", "a138", "a139", "a140", "a141", "a142", "a143", "a144", "a145", "a146", "a147", "a148", "a149", "a150", "a151", "a152", "a153", "a154", "a155", "a156", "a157", "a158", "a159", "a160", "a161", "a162", "a163", "a164", "a165", "a166", "a167", "a168", "a169", "a170", "a171", "a172", "a173", "a174", "a175", "a176", "a177", "a178", "a179", "a180", "a181", "a182", "a183", "a184", "a185", "a186", "a187", "a188", "a189", "a190", "a191", "a192", "a193", "a194", "a195", "a196", "a197", "a198", "a199", "a200", "a201", "a202", "a203", "a204", "a205", "a206", "a207", "a208", "a209", "a210", "a211", "a212", "a213", "a214", "a215", "a216", "a217", "a218", "a219", "a220", "a221", "a222", "a223", "a224", "a225", "a226", "a227", "a228", "a229", "a230", "a231", "a232", "a233", "a234", "a235", "a236", "a237", "a238", "a239", "a240", "a241", "a242", "a243", "a244", "a245", "a246", "a247", "a248", "a249", "a250", "a251", "a252", "a253", "a254", "a255"
-template <int R>
+// The 8-wave kernels (wide8, rs) hard-wire a[0 .. 127] in the same way and name exactly those 128: that is what lets two of
+// their waves share a SIMD.  The clobber lists "a0" ... "a127" and "a128" ... "a255", ten names per RR_A10:
+#define RR_A10(p) "a" #p "0", "a" #p "1", "a" #p "2", "a" #p "3", "a" #p "4", "a" #p "5", "a" #p "6", "a" #p "7", "a" #p "8", "a" #p "9"
+#define RR_AGPRS_0_127                                                                                                             \
+  RR_A10(), RR_A10(1), RR_A10(2), RR_A10(3), RR_A10(4), RR_A10(5), RR_A10(6), RR_A10(7), RR_A10(8), RR_A10(9), RR_A10(10), RR_A10(11), \
+      "a120", "a121", "a122", "a123", "a124", "a125", "a126", "a127"
+#define RR_AGPRS_128_255                                                                                                           \
+  "a128", "a129", RR_A10(13), RR_A10(14), RR_A10(15), RR_A10(16), RR_A10(17), RR_A10(18), RR_A10(19), RR_A10(20), RR_A10(21),      \
+      RR_A10(22), RR_A10(23), RR_A10(24), "a250", "a251", "a252", "a253", "a254", "a255"
+// An asm statement over the NACC = 256 or 128 fixed accumulators.  The arguments after NACC are the statement up to and including
+// its inputs - "template" : outputs : inputs, with both colons even where a list is empty - because the clobber list is spliced
+// on behind a third colon.
+#define RR_ASM_FIXED_ACC(NACC, ...)                                                          \
+  do {                                                                                       \
+    static_assert(NACC == 256 || NACC == 128, "fixed accumulators: a0 .. a255 or a0 .. a127"); \
+    if constexpr (NACC == 256) asm volatile(__VA_ARGS__ : RR_AGPRS_0_127, RR_AGPRS_128_255); \
+    else asm volatile(__VA_ARGS__ : RR_AGPRS_0_127);                                         \
+  } while (0)
+template <int NACC, int R>
 __device__ __forceinline__ f32x4 read_acc_fixed() {
   f32x4 v;
-  asm volatile("v_accvgpr_read_b32 %0, a[%4]\n\tv_accvgpr_read_b32 %1, a[%5]\n\tv_accvgpr_read_b32 %2, a[%6]\n\tv_accvgpr_read_b32 %3, a[%7]"
-               : "=v"(v[0]), "=v"(v[1]), "=v"(v[2]), "=v"(v[3]) : "n"(R), "n"(R + 1), "n"(R + 2), "n"(R + 3) : RR_ALL_AGPRS);
+  RR_ASM_FIXED_ACC(NACC, "v_accvgpr_read_b32 %0, a[%4]\n\tv_accvgpr_read_b32 %1, a[%5]\n\tv_accvgpr_read_b32 %2, a[%6]\n\tv_accvgpr_read_b32 %3, a[%7]"
+                   : "=v"(v[0]), "=v"(v[1]), "=v"(v[2]), "=v"(v[3]) : "n"(R), "n"(R + 1), "n"(R + 2), "n"(R + 3));
   return v;
 }
+template <typename T, int NACC> struct Mfma16Fixed;   // MFMA of two VGPR fragments into the fixed accumulator a[R .. R+3]
+#define RR_MFMA16F(NAME, MNEMONIC, FRAG)                                                                                   \
+  template <int NACC> struct Mfma16Fixed<NAME, NACC> {                                                                     \
+    template <int R, bool FIRST>                                                                                           \
+    static __device__ __forceinline__ void run(const FRAG& a, const FRAG& b) {                                             \
+      if (FIRST) RR_ASM_FIXED_ACC(NACC, MNEMONIC " a[%2:%3], %0, %1, 0" ::"v"(a), "v"(b), "n"(R), "n"(R + 3));             \
+      else RR_ASM_FIXED_ACC(NACC, MNEMONIC " a[%2:%3], %0, %1, a[%2:%3]" ::"v"(a), "v"(b), "n"(R), "n"(R + 3));            \
+    }                                                                                                                      \
+  };
+RR_MFMA16F(_Float16, "v_mfma_f32_16x16x32_f16", f16x8)
+RR_MFMA16F(__bf16, "v_mfma_f32_16x16x32_bf16", bf16x8)
+#undef RR_MFMA16F
 
 // K rotation (rows wider than 1536 elements).  Every K step of a group reads a 128-byte column slab of 256 rows; with a row pitch
 // of 4 or 8 KiB (d = 2048, 4096) those 256 addresses fall on a handful of HBM channels, and workgroups that walk the K steps in
@@ -71,12 +108,25 @@ __device__ __forceinline__ int wide_group_rotation(const ScanArgs& a, uint32_t g
 }
 __device__ __forceinline__ int wide_rotated(int kg, int rot, int KG) { return kg + rot >= KG ? kg + rot - KG : kg + rot; }
 
-template <typename F>
-__device__ __forceinline__ void vm_drain_tied(F& r0, F& r1) {  // every vector-memory op has landed before r0 / r1 can be reused
-  asm volatile("s_waitcnt vmcnt(0)" : "+v"(r0), "+v"(r1)::"memory");
+// L2 metric: rank by q.x - |x|^2/2.  Subtracts the half squared norms of the lane's 2 x 4 rows of tile ordinal j from its NQB
+// accumulator blocks (an L2 search is never segmented: no cursor; rows past the end are clamped here and filtered by id later).
+template <int NQB>
+__device__ __forceinline__ void subtract_half_sqnorms(const ScanArgs& a, uint32_t j, int g, f32x4 (&e)[2][4]) {
+  const uint32_t r0 = (a.tile_first + j * a.tile_stride) * kTileRows + 4 * g;
+  f32x4 h0, h1;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    h0[i] = a.half_sqnorm[r0 + i < a.n_rows ? r0 + i : a.n_rows - 1];
+    h1[i] = a.half_sqnorm[r0 + 16 + i < a.n_rows ? r0 + 16 + i : a.n_rows - 1];
+  }
+#pragma unroll
+  for (int qb = 0; qb < NQB; ++qb) {
+    e[0][qb] -= h0;
+    e[1][qb] -= h1;
+  }
 }
 
-// ---- four waves, deep pipeline (round 2) --------------------------------------------------------------------------------
+// ---- query prefetch of the pd and wide8 kernels (round 2: four waves, deep pipeline) -----------------------------------------
 // vmcnt retires in order, so a wave that loads the queries of step s+1 behind the DMA of the steps after it and waits for them
 // at the end of step s also waits for every slab issued before them: whatever the ring depth, only ONE slab (32 KB per CU) is
 // then in flight past a step boundary - 2/3 of what the d <= 768 kernel keeps (PMC of that form, profiles/r02/wide_*: waves in
@@ -85,12 +135,8 @@ __device__ __forceinline__ void vm_drain_tied(F& r0, F& r1) {  // every vector-m
 // (PD+2 slots), so the closing wait of step s - vmcnt(8 (2 PD - 1)) - leaves PD slabs and PD-1 query sets in flight:
 //   issue order      ... DMA(s+1) | q(s+1) | DMA(s+2) | q(s+2) | ... | DMA(s+PD+1)
 //   closing wait(s)      <- landed ------->| <- may still be in flight ----------->
-// The query buffers are INPUT-ONLY operands of every asm statement that touches them (the loads included): hipcc sees PD+1
-// sets of loop-invariant values that it must keep in fixed registers, and has no definition point inside the loop at which
-// it could insert the register copies that read a destination before its load has landed (the failure mode of "=v" loads
-// whose values are live around a back-edge).  wave_compact is inlined here: a call would spill the caller-saved part of
-// those buffers around it and restore stale copies over loads that landed meanwhile.
-// (the base goes through readfirstlane: it is uniform by construction, but should hipcc's divergence analysis ever think
+// The helpers below are that discipline; the two kernels differ in where a step places its loads inside the MFMA stream.
+// (the base of a query load goes through readfirstlane: it is uniform by construction, but should hipcc's divergence analysis ever think
 // otherwise it would hand the "s" operand a VGPR pair - seen in a diagnostic build - and the instruction would not assemble)
 __device__ __forceinline__ const void* uniform_ptr(const void* p) {
   const uint64_t v = (uint64_t)p;
@@ -101,23 +147,75 @@ template <typename F>
 __device__ __forceinline__ void query_load_into(const F& dst, uint32_t lane_off, const void* sbase, int imm) {
   asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" ::"v"(dst), "v"(lane_off), "s"(uniform_ptr(sbase)), "n"(imm) : "memory");
 }
-template <typename T> struct Mfma16FixedIn;
-#define RR_MFMA16FI(NAME, MNEMONIC, FRAG)                                                                            \
-  template <> struct Mfma16FixedIn<NAME> {                                                                           \
-    template <int R, bool FIRST>                                                                                     \
-    static __device__ __forceinline__ void run(const FRAG& a, const FRAG& b) {                                       \
-      if (FIRST) asm volatile(MNEMONIC " a[%2:%3], %0, %1, 0" ::"v"(a), "v"(b), "n"(R), "n"(R + 3) : RR_ALL_AGPRS);  \
-      else asm volatile(MNEMONIC " a[%2:%3], %0, %1, a[%2:%3]" ::"v"(a), "v"(b), "n"(R), "n"(R + 3) : RR_ALL_AGPRS); \
-    }                                                                                                                \
-  };
-RR_MFMA16FI(_Float16, "v_mfma_f32_16x16x32_f16", f16x8)
-RR_MFMA16FI(__bf16, "v_mfma_f32_16x16x32_bf16", bf16x8)
-#undef RR_MFMA16FI
-
 // The pd / wide8 kernels' query loads read prep_kernel's fragment-order copy (a.xqs: one contiguous KiB per instruction, not 16
 // rows x 64 B of the row-major block)
 constexpr int kWideQStep = 2048;   // bytes per 64-wide K step: two 32-wide k slices of 64 lanes x 16 B
 constexpr int kWideQPar = 1024;    // ... per k slice
+// The query buffers q[buffer][query block][k slice] are INPUT-ONLY operands of every asm statement that touches them (the loads
+// included): hipcc sees PD+1 sets of loop-invariant values that it must keep in fixed registers, and has no definition point
+// inside the loop at which it could insert the register copies that read a destination before its load has landed (the failure
+// mode of "=v" loads whose values are live around a back-edge).  This is their one definition, ahead of the loop.  wave_compact
+// is inlined in these kernels: a call would spill the caller-saved part of those buffers around it and restore stale copies over
+// loads that landed meanwhile.
+template <typename F, int QB, int NQB>
+__device__ __forceinline__ void pin_query_buffers(F (&q)[QB][NQB][2]) {
+#pragma unroll
+  for (int b = 0; b < QB; ++b)
+#pragma unroll
+    for (int qb = 0; qb < NQB; ++qb) {
+      asm volatile("; query buffer %0" : "=v"(q[b][qb][0]));
+      asm volatile("; query buffer %0" : "=v"(q[b][qb][1]));
+    }
+}
+// the wave's queries of K column kg -> buffer B
+template <int B, typename F, int QB, int NQB>
+__device__ __forceinline__ void load_queries(const F (&q)[QB][NQB][2], const uint32_t (&qoff)[NQB], const void* xqs, int kg) {
+  const char* sb = (const char*)xqs + (size_t)kg * kWideQStep;
+#pragma unroll
+  for (int qb = 0; qb < NQB; ++qb) {
+    query_load_into(q[B][qb][0], qoff[qb], sb, 0);
+    query_load_into(q[B][qb][1], qoff[qb], sb, kWideQPar);
+  }
+}
+// end of step s: slab s+1 (this wave's pieces) and q(s+1) have landed.  WAIT_Q: vector-memory ops younger than q(s+1) for a wave
+// that holds queries (nb > 0), WAIT_0: for one without - DMA(s+2) .. DMA(s+LEAD) only.
+template <int WAIT_Q, int WAIT_0>
+__device__ __forceinline__ void closing_wait(int nb) {
+  static_assert(WAIT_Q <= 63 && WAIT_0 <= WAIT_Q, "vmcnt range");
+  if (nb > 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAIT_Q) : "memory");
+  else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAIT_0) : "memory");
+}
+// one K step of the main loop: step(phase, first) with both as compile-time tags - phase names the query buffer the step
+// multiplies (and, by it, the one it refills), first (kg == 0) makes its MFMAs start the accumulators instead of adding to them.
+// phase and first come by reference to the kernel's own variables and the selecting lambda is always_inline on purpose: with
+// by-value parameters and a plain lambda (two forms built) hipcc laid the 2 QB step bodies out differently - 40 of the 44 kernels
+// of this file lost their parent hot region and grew by about 70 instructions each.
+template <int QB, typename S>
+__device__ __forceinline__ void dispatch_step(const int& phase, const bool& first, S& step) {
+  static_for<QB>([&](auto pi) __attribute__((always_inline)) {
+    if (phase == decltype(pi)::value) {
+      if (first) step(pi, std::true_type{});
+      else step(pi, std::false_type{});
+    }
+  });
+}
+// No LDS-DMA may outlive the workgroup - and no prefetched query load may outlive the LOOP: the sets of the steps that will
+// never run are still landing in the q registers, which hipcc regards as free from here on.  It computed the addresses of the
+// tail's stores in them BEFORE an untied wait (ALU work is not ordered by a "memory" clobber) and a late load then overwrote
+// the address: wild stores, intermittently, and only where the buffer in flight at loop exit was one the tail reuses (the
+// few-query kernel at d = 2048, KG mod 3 == 2).  The wait therefore names every q register as in/out: nothing of the tail
+// can be placed in them before it has executed.
+template <typename F>
+__device__ __forceinline__ void vm_drain_tied(F& r0, F& r1) {  // every vector-memory op has landed before r0 / r1 can be reused
+  asm volatile("s_waitcnt vmcnt(0)" : "+v"(r0), "+v"(r1)::"memory");
+}
+template <typename F, int QB, int NQB>
+__device__ __forceinline__ void drain_query_buffers(F (&q)[QB][NQB][2]) {
+  static_for<QB * NQB>([&](auto i) {
+    constexpr int b = decltype(i)::value / NQB, qb = decltype(i)::value % NQB;
+    vm_drain_tied(q[b][qb][0], q[b][qb][1]);
+  });
+}
 // DENSE launches (bootstrap sample, corpora <= 8192 rows) cover at most 256 tiles: with 8-tile groups only 32 workgroups would
 // have work and each would still walk the whole K loop (112 us at d = 4096), so they use one tile per group.
 template <typename T, bool DENSE, bool L2, int NQB>
@@ -139,7 +237,6 @@ __global__ __launch_bounds__(256, 1) void flat_scan_wide_pd_kernel(const ScanArg
   constexpr int QPW = 16 * NQB;
   constexpr int WAIT_Q = NT * PD + NQL * (PD - 1);  // ops younger than q(s+1) at the end of step s (waves holding queries)
   constexpr int WAIT_0 = NT * PD;                   // ... for a wave without queries: DMA(s+2) .. DMA(s+LEAD)
-  static_assert(WAIT_Q <= 63, "vmcnt range");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -149,16 +246,10 @@ __global__ __launch_bounds__(256, 1) void flat_scan_wide_pd_kernel(const ScanArg
   const uint32_t n_groups = (n_tiles + NT - 1) / NT;
 
   uint32_t roff[2];
-  {
-    const int rho = col & 7, p = col >> 3;
-    const int f = ((rho >> 1) & 3) | (p << 2);
 #pragma unroll
-    for (int par = 0; par < 2; ++par) roff[par] = p * 1024 + rho * 128 + (((4 * par + g) ^ f) * 16);
-  }
+  for (int par = 0; par < 2; ++par) roff[par] = kgroup_frag_offset(col >> 3, col & 7, par, g);
   // DMA side: this wave's piece of tile t = rows 8*wave .. +7, lane -> (row rho_w, 16-byte chunk c_w)
-  const int rho_w = lane >> 3, sig = lane & 7;
-  const int f_w = ((rho_w >> 1) & 3) | ((wave & 1) << 2);
-  const int c_w = sig ^ f_w;
+  const int rho_w = lane >> 3, c_w = kgroup_dma_chunk(lane, wave & 1);
   // Source addresses: one uniform base per (group, K step) + a 32-bit lane offset per tile, recomputed once per group (the
   // per-piece 64-bit row arithmetic of the round-1 kernel cost 9 VALU + 5 SALU per piece, 8 pieces per step).
   const size_t row_bytes = (size_t)D * 2;
@@ -210,23 +301,8 @@ __global__ __launch_bounds__(256, 1) void flat_scan_wide_pd_kernel(const ScanArg
   // the thresholds are global loads: land them here, or their first use inside the loop drains the DMA ring
   asm volatile("s_waitcnt vmcnt(0)" : "+v"(st.thr[0]), "+v"(st.thr[1]), "+v"(st.thr[2]), "+v"(st.thr[3]));
 
-  frag q[QB][NQB][2];                      // [buffer][query block][k slice]: input-only operands everywhere (see above)
-#pragma unroll
-  for (int b = 0; b < QB; ++b)
-#pragma unroll
-    for (int qb = 0; qb < NQB; ++qb) {
-      asm volatile("; query buffer %0" : "=v"(q[b][qb][0]));
-      asm volatile("; query buffer %0" : "=v"(q[b][qb][1]));
-    }
-  auto load_queries = [&](auto buf_tag, int kg) {
-    constexpr int B = decltype(buf_tag)::value;
-    const char* sb = (const char*)a.xqs + (size_t)kg * kWideQStep;
-#pragma unroll
-    for (int qb = 0; qb < NQB; ++qb) {
-      query_load_into(q[B][qb][0], qoff[qb], sb, 0);
-      query_load_into(q[B][qb][1], qoff[qb], sb, kWideQPar);
-    }
-  };
+  frag q[QB][NQB][2];                      // [buffer][query block][k slice]
+  pin_query_buffers(q);
 
   uint32_t grp = blockIdx.x;               // group being multiplied
   uint32_t dgrp = blockIdx.x;              // group / K step the DMA stream is at (LEAD steps ahead)
@@ -241,19 +317,15 @@ __global__ __launch_bounds__(256, 1) void flat_scan_wide_pd_kernel(const ScanArg
     for (int t = 0; t < NT; ++t) issue_piece(dkg, dslot, t);
     dma_advance();
   };
-  auto closing_wait = [&]() {
-    if (nb > 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAIT_Q) : "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAIT_0) : "memory");
-  };
   if (grp < n_groups) {
     dma_new_group(dgrp);
     // prologue in the steady-state issue order: DMA(0) | q(0) DMA(1) | q(1) DMA(2) | ... | q(PD-1) DMA(PD)
     dma_slab();
     static_for<PD>([&](auto i) {
-      if (nb > 0) load_queries(i, wide_rotated(decltype(i)::value, rot, KG));
+      if (nb > 0) load_queries<decltype(i)::value>(q, qoff, a.xqs, wide_rotated(decltype(i)::value, rot, KG));
       dma_slab();
     });
-    closing_wait();                        // DMA(0) and q(0) have landed
+    closing_wait<WAIT_Q, WAIT_0>(nb);      // DMA(0) and q(0) have landed
   }
 
   int slot = 0, phase = 0, kg = 0;
@@ -282,17 +354,10 @@ __global__ __launch_bounds__(256, 1) void flat_scan_wide_pd_kernel(const ScanArg
       static_for<NF>([&](auto fi) {
         constexpr int f = decltype(fi)::value;
         constexpr int t = f >> 2, par = (f >> 1) & 1, rb = f & 1;
-        if (NF - f >= NB) lgkm_wait<NB - 1>();
-        else if (NF - f == 7) lgkm_wait<6>();
-        else if (NF - f == 6) lgkm_wait<5>();
-        else if (NF - f == 5) lgkm_wait<4>();
-        else if (NF - f == 4) lgkm_wait<3>();
-        else if (NF - f == 3) lgkm_wait<2>();
-        else if (NF - f == 2) lgkm_wait<1>();
-        else lgkm_wait<0>();
+        lgkm_wait_left<NF - f, NB>();
         static_for<NQB>([&](auto qi) {
           constexpr int qb = decltype(qi)::value;
-          Mfma16FixedIn<T>::template run<16 * (2 * t + rb) + 4 * qb, FIRST && par == 0>(c[f % NB], q[P][qb][par]);
+          Mfma16Fixed<T, 256>::template run<16 * (2 * t + rb) + 4 * qb, FIRST && par == 0>(c[f % NB], q[P][qb][par]);
         });
         if (f + NB < NF) {
           constexpr int fn = f + NB;
@@ -303,7 +368,7 @@ __global__ __launch_bounds__(256, 1) void flat_scan_wide_pd_kernel(const ScanArg
             query_load_into(q[PN][f >> 2][(f >> 1) & 1], qoff[f >> 2], qsb, ((f >> 1) & 1) * kWideQPar);
           if constexpr ((f & 1) == 1 && f >= 16) issue_piece(dkg, dslot, (f - 16) >> 1);
         } else {
-          if (f == 0) load_queries(std::integral_constant<int, PN>{}, nkg);
+          if (f == 0) load_queries<PN>(q, qoff, a.xqs, nkg);
           if ((f & 3) == 1) issue_piece(dkg, dslot, f >> 2);
         }
       });
@@ -313,7 +378,7 @@ __global__ __launch_bounds__(256, 1) void flat_scan_wide_pd_kernel(const ScanArg
     }
     dma_advance();
     if (++slot == NS) slot = 0;
-    closing_wait();                        // slab s+1 (this wave's pieces) and q(s+1) have landed
+    closing_wait<WAIT_Q, WAIT_0>(nb);
   };
   auto read_tile = [&](auto r_tag, f32x4 (&e)[2][4]) {
     constexpr int R = decltype(r_tag)::value;
@@ -321,18 +386,13 @@ __global__ __launch_bounds__(256, 1) void flat_scan_wide_pd_kernel(const ScanArg
     for (int qb = 0; qb < 4; ++qb) e[0][qb] = e[1][qb] = f32x4{0.f, 0.f, 0.f, 0.f};
     static_for<NQB>([&](auto qi) {
       constexpr int qb = decltype(qi)::value;
-      e[0][qb] = read_acc_fixed<R + 4 * qb>();
-      e[1][qb] = read_acc_fixed<R + 16 + 4 * qb>();
+      e[0][qb] = read_acc_fixed<256, R + 4 * qb>();
+      e[1][qb] = read_acc_fixed<256, R + 16 + 4 * qb>();
     });
   };
   while (grp < n_groups) {
     const bool first = kg == 0;
-    static_for<QB>([&](auto pi) {
-      if (phase == decltype(pi)::value) {
-        if (first) step(pi, std::true_type{});
-        else step(pi, std::false_type{});
-      }
-    });
+    dispatch_step<QB>(phase, first, step);
     phase = phase + 1 == QB ? 0 : phase + 1;
     if (++kg < KG) continue;
     kg = 0;
@@ -345,20 +405,7 @@ __global__ __launch_bounds__(256, 1) void flat_scan_wide_pd_kernel(const ScanArg
         if (j < n_tiles) {
           f32x4 e[2][4];
           read_tile(std::integral_constant<int, 32 * t>{}, e);
-          if (L2) {  // rank by q.x - |x|^2/2: the lane's 2 x 4 rows of this tile (rows past the end are filtered by id later)
-            const uint32_t r0 = (a.tile_first + j * a.tile_stride) * kTileRows + 4 * g;
-            f32x4 h0, h1;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              h0[i] = a.half_sqnorm[r0 + i < a.n_rows ? r0 + i : a.n_rows - 1];
-              h1[i] = a.half_sqnorm[r0 + 16 + i < a.n_rows ? r0 + 16 + i : a.n_rows - 1];
-            }
-#pragma unroll
-            for (int qb = 0; qb < NQB; ++qb) {
-              e[0][qb] -= h0;
-              e[1][qb] -= h1;
-            }
-          }
+          if (L2) subtract_half_sqnorms<NQB>(a, j, g, e);
           tile_epilogue16<DENSE, NQB, QPW, true, 4>(a, st, e, j, lane, wave);
         }
       });
@@ -367,16 +414,7 @@ __global__ __launch_bounds__(256, 1) void flat_scan_wide_pd_kernel(const ScanArg
     rot = rot_next;
     rot_next = wide_group_rotation(a, grp + gridDim.x, NT, KG);
   }
-  // No LDS-DMA may outlive the workgroup - and no prefetched query load may outlive the LOOP: the sets of the steps that will
-  // never run are still landing in the q registers, which hipcc regards as free from here on.  It computed the addresses of the
-  // stores below in them BEFORE an untied wait (ALU work is not ordered by a "memory" clobber) and a late load then overwrote
-  // the address: wild stores, intermittently, and only where the buffer in flight at loop exit was one the tail reuses (the
-  // few-query kernel at d = 2048, KG mod 3 == 2).  The wait therefore names every q register as in/out: nothing of the tail
-  // can be placed in them before it has executed.
-  static_for<QB * NQB>([&](auto i) {
-    constexpr int b = decltype(i)::value / NQB, qb = decltype(i)::value % NQB;
-    vm_drain_tied(q[b][qb][0], q[b][qb][1]);
-  });
+  drain_query_buffers(q);
   if (!DENSE) {
 #pragma unroll
     for (int qb = 0; qb < NQB; ++qb) a.cand_cnt[(wave * QPW + qb * 16 + col) * nbuf + blockIdx.x * 4 + g] = st.cnt[qb];
@@ -393,26 +431,6 @@ __global__ __launch_bounds__(256, 1) void flat_scan_wide_pd_kernel(const ScanArg
 // AGPR accumulators, 128 VGPRs): while one wave of a SIMD is stuck issuing a load, its partner's MFMAs use the pipe.  Same
 // LDS image, same ring and queue discipline as above with 4 DMA pieces and 4 query loads per wave and step; every A fragment
 // is read from LDS by 8 waves instead of 4 (256 KB per step and CU = half of the LDS read rate).
-#define RR_AGPRS_128 "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", "a10", "a11", "a12", "a13", "a14", "a15", "a16", "a17", "a18", "a19", "a20", "a21", "a22", "a23", "a24", "a25", "a26", "a27", "a28", "a29", "a30", "a31", "a32", "a33", "a34", "a35", "a36", "a37", "a38", "a39", "a40", "a41", "a42", "a43", "a44", "a45", "a46", "a47", "a48", "a49", "a50", "a51", "a52", "a53", "a54", "a55", "a56", "a57", "a58", "a59", "a60", "a61", "a62", "a63", "a64", "a65", "a66", "a67", "a68", "a69", "a70", "a71", "a72", "a73", "a74", "a75", "a76", "a77", "a78", "a79", "a80", "a81", "a82", "a83", "a84", "a85", "a86", "a87", "a88", "a89", "a90", "a91", "a92", "a93", "a94", "a95", "a96", "a97", "a98", "a99", "a100", "a101", "a102", "a103", "a104", "a105", "a106", "a107", "a108", "a109", "a110", "a111", "a112", "a113", "a114", "a115", "a116", "a117", "a118", "a119", "a120", "a121", "a122", "a123", "a124", "a125", "a126", "a127"
-template <typename T> struct Mfma16Fixed128;
-#define RR_MFMA16F128(NAME, MNEMONIC, FRAG)                                                                          \
-  template <> struct Mfma16Fixed128<NAME> {                                                                          \
-    template <int R, bool FIRST>                                                                                     \
-    static __device__ __forceinline__ void run(const FRAG& a, const FRAG& b) {                                       \
-      if (FIRST) asm volatile(MNEMONIC " a[%2:%3], %0, %1, 0" ::"v"(a), "v"(b), "n"(R), "n"(R + 3) : RR_AGPRS_128);  \
-      else asm volatile(MNEMONIC " a[%2:%3], %0, %1, a[%2:%3]" ::"v"(a), "v"(b), "n"(R), "n"(R + 3) : RR_AGPRS_128); \
-    }                                                                                                                \
-  };
-RR_MFMA16F128(_Float16, "v_mfma_f32_16x16x32_f16", f16x8)
-RR_MFMA16F128(__bf16, "v_mfma_f32_16x16x32_bf16", bf16x8)
-#undef RR_MFMA16F128
-template <int R>
-__device__ __forceinline__ f32x4 read_acc_fixed128() {
-  f32x4 v;
-  asm volatile("v_accvgpr_read_b32 %0, a[%4]\n\tv_accvgpr_read_b32 %1, a[%5]\n\tv_accvgpr_read_b32 %2, a[%6]\n\tv_accvgpr_read_b32 %3, a[%7]"
-               : "=v"(v[0]), "=v"(v[1]), "=v"(v[2]), "=v"(v[3]) : "n"(R), "n"(R + 1), "n"(R + 2), "n"(R + 3) : RR_AGPRS_128);
-  return v;
-}
 
 template <typename T, bool L2, int NQB>
 __global__ __launch_bounds__(512) void flat_scan_wide8_kernel(const ScanArgs a, const int D) {
@@ -437,17 +455,11 @@ __global__ __launch_bounds__(512) void flat_scan_wide8_kernel(const ScanArgs a, 
   const uint32_t n_groups = (n_tiles + NT - 1) / NT;
 
   uint32_t roff[2];
-  {
-    const int rho = col & 7, p = col >> 3;
-    const int f = ((rho >> 1) & 3) | (p << 2);
 #pragma unroll
-    for (int par = 0; par < 2; ++par) roff[par] = p * 1024 + rho * 128 + (((4 * par + g) ^ f) * 16);
-  }
+  for (int par = 0; par < 2; ++par) roff[par] = kgroup_frag_offset(col >> 3, col & 7, par, g);
   // DMA side: wave w fills row octet o = w & 3 (rows 8 o .. +7) of tiles 4 (w >> 2) .. +3; lane -> (row rho_w, 16-byte chunk c_w)
   const int oct = wave & 3, tbase = (wave >> 2) * 4;
-  const int rho_w = lane >> 3, sig = lane & 7;
-  const int f_w = ((rho_w >> 1) & 3) | ((oct & 1) << 2);
-  const int c_w = sig ^ f_w;
+  const int rho_w = lane >> 3, c_w = kgroup_dma_chunk(lane, oct & 1);
   const size_t row_bytes = (size_t)D * 2;
   const char* dbase = (const char*)a.xb;
   uint32_t voff[NPW];
@@ -493,23 +505,8 @@ __global__ __launch_bounds__(512) void flat_scan_wide8_kernel(const ScanArgs a, 
   }
   asm volatile("s_waitcnt vmcnt(0)" : "+v"(st.thr[0]), "+v"(st.thr[1]));
 
-  frag q[QB][NQB][2];
-#pragma unroll
-  for (int b = 0; b < QB; ++b)
-#pragma unroll
-    for (int qb = 0; qb < NQB; ++qb) {
-      asm volatile("; query buffer %0" : "=v"(q[b][qb][0]));
-      asm volatile("; query buffer %0" : "=v"(q[b][qb][1]));
-    }
-  auto load_queries = [&](auto buf_tag, int kg) {
-    constexpr int B = decltype(buf_tag)::value;
-    const char* sb = (const char*)a.xqs + (size_t)kg * kWideQStep;
-#pragma unroll
-    for (int qb = 0; qb < NQB; ++qb) {
-      query_load_into(q[B][qb][0], qoff[qb], sb, 0);
-      query_load_into(q[B][qb][1], qoff[qb], sb, kWideQPar);
-    }
-  };
+  frag q[QB][NQB][2];                      // [buffer][query block][k slice]
+  pin_query_buffers(q);
 
   uint32_t grp = blockIdx.x, dgrp = blockIdx.x;
   int dkg = 0, dslot = 0;
@@ -523,18 +520,14 @@ __global__ __launch_bounds__(512) void flat_scan_wide8_kernel(const ScanArgs a, 
     for (int i = 0; i < NPW; ++i) issue_piece(dkg, dslot, i);
     dma_advance();
   };
-  auto closing_wait = [&]() {
-    if (nb > 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAIT_Q) : "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAIT_0) : "memory");
-  };
   if (grp < n_groups) {
     dma_new_group(dgrp);
     dma_slab();
     static_for<PD>([&](auto i) {
-      if (nb > 0) load_queries(i, wide_rotated(decltype(i)::value, rot, KG));
+      if (nb > 0) load_queries<decltype(i)::value>(q, qoff, a.xqs, wide_rotated(decltype(i)::value, rot, KG));
       dma_slab();
     });
-    closing_wait();
+    closing_wait<WAIT_Q, WAIT_0>(nb);
   }
 
   int slot = 0, phase = 0, kg = 0;
@@ -546,7 +539,7 @@ __global__ __launch_bounds__(512) void flat_scan_wide8_kernel(const ScanArgs a, 
     __builtin_amdgcn_s_barrier();
     if (nb > 0) {
       const int nkg = kg + PD >= KG ? wide_rotated(kg + PD - KG, rot_next, KG) : wide_rotated(kg + PD, rot, KG);
-      load_queries(std::integral_constant<int, PN>{}, nkg);
+      load_queries<PN>(q, qoff, a.xqs, nkg);
       frag c[NB];
       const uint32_t ab0 = (uint32_t)(slot * STEP_BYTES) + roff[0], ab1 = (uint32_t)(slot * STEP_BYTES) + roff[1];
 #pragma unroll
@@ -554,11 +547,10 @@ __global__ __launch_bounds__(512) void flat_scan_wide8_kernel(const ScanArgs a, 
       static_for<NF>([&](auto fi) {
         constexpr int f = decltype(fi)::value;
         constexpr int t = f >> 2, par = (f >> 1) & 1, rb = f & 1;
-        constexpr int LEFT = NF - f;       // fragments not yet consumed; min(LEFT, NB) - 1 reads may stay in flight
-        lgkm_wait<(LEFT >= NB ? NB : LEFT) - 1>();
+        lgkm_wait_left<NF - f, NB>();
         static_for<NQB>([&](auto qi) {
           constexpr int qb = decltype(qi)::value;
-          Mfma16Fixed128<T>::template run<8 * (2 * t + rb) + 4 * qb, FIRST && par == 0>(c[f % NB], q[P][qb][par]);
+          Mfma16Fixed<T, 128>::template run<8 * (2 * t + rb) + 4 * qb, FIRST && par == 0>(c[f % NB], q[P][qb][par]);
         });
         if constexpr (f + NB < NF) {
           constexpr int fn = f + NB;
@@ -572,16 +564,11 @@ __global__ __launch_bounds__(512) void flat_scan_wide8_kernel(const ScanArgs a, 
     }
     dma_advance();
     if (++slot == NS) slot = 0;
-    closing_wait();
+    closing_wait<WAIT_Q, WAIT_0>(nb);
   };
   while (grp < n_groups) {
     const bool first = kg == 0;
-    static_for<QB>([&](auto pi) {
-      if (phase == decltype(pi)::value) {
-        if (first) step(pi, std::true_type{});
-        else step(pi, std::false_type{});
-      }
-    });
+    dispatch_step<QB>(phase, first, step);
     phase = phase + 1 == QB ? 0 : phase + 1;
     if (++kg < KG) continue;
     kg = 0;
@@ -597,23 +584,10 @@ __global__ __launch_bounds__(512) void flat_scan_wide8_kernel(const ScanArgs a, 
           for (int qb = 0; qb < 4; ++qb) e[0][qb] = e[1][qb] = f32x4{0.f, 0.f, 0.f, 0.f};
           static_for<NQB>([&](auto qi) {
             constexpr int qb = decltype(qi)::value;
-            e[0][qb] = read_acc_fixed128<16 * t + 4 * qb>();
-            e[1][qb] = read_acc_fixed128<16 * t + 8 + 4 * qb>();
+            e[0][qb] = read_acc_fixed<128, 16 * t + 4 * qb>();
+            e[1][qb] = read_acc_fixed<128, 16 * t + 8 + 4 * qb>();
           });
-          if (L2) {
-            const uint32_t r0 = (a.tile_first + j * a.tile_stride) * kTileRows + 4 * g;
-            f32x4 h0, h1;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              h0[i] = a.half_sqnorm[r0 + i < a.n_rows ? r0 + i : a.n_rows - 1];
-              h1[i] = a.half_sqnorm[r0 + 16 + i < a.n_rows ? r0 + 16 + i : a.n_rows - 1];
-            }
-#pragma unroll
-            for (int qb = 0; qb < NQB; ++qb) {
-              e[0][qb] -= h0;
-              e[1][qb] -= h1;
-            }
-          }
+          if (L2) subtract_half_sqnorms<NQB>(a, j, g, e);
           tile_epilogue16<false, NQB, QPW, true, 8>(a, st, e, j, lane, wave);
         }
       });
@@ -622,11 +596,7 @@ __global__ __launch_bounds__(512) void flat_scan_wide8_kernel(const ScanArgs a, 
     rot = rot_next;
     rot_next = wide_group_rotation(a, grp + gridDim.x, NT, KG);
   }
-  // (the wait is tied to every q register: see the end of flat_scan_wide_pd_kernel)
-  static_for<QB * NQB>([&](auto i) {
-    constexpr int b = decltype(i)::value / NQB, qb = decltype(i)::value % NQB;
-    vm_drain_tied(q[b][qb][0], q[b][qb][1]);
-  });
+  drain_query_buffers(q);
 #pragma unroll
   for (int qb = 0; qb < NQB; ++qb) a.cand_cnt[(wave * QPW + qb * 16 + col) * nbuf + blockIdx.x * 4 + g] = st.cnt[qb];
 }
@@ -662,17 +632,11 @@ __global__ __launch_bounds__(512) void flat_scan_wide_rs_kernel(const ScanArgs a
   const uint32_t n_groups = (n_tiles + NT - 1) / NT;
 
   uint32_t roff[2];
-  {
-    const int rho = col & 7, p = col >> 3;
-    const int f = ((rho >> 1) & 3) | (p << 2);
 #pragma unroll
-    for (int par = 0; par < 2; ++par) roff[par] = p * 1024 + rho * 128 + (((4 * par + g) ^ f) * 16);
-  }
+  for (int par = 0; par < 2; ++par) roff[par] = kgroup_frag_offset(col >> 3, col & 7, par, g);
   // DMA side, both slabs: wave w fills row octet o = w & 3 (rows / queries 8 o .. +7) of tiles 4 (w >> 2) .. +3
   const int oct = wave & 3, tbase = (wave >> 2) * 4;
-  const int rho_w = lane >> 3, sig = lane & 7;
-  const int f_w = ((rho_w >> 1) & 3) | ((oct & 1) << 2);
-  const int c_w = sig ^ f_w;
+  const int rho_w = lane >> 3, c_w = kgroup_dma_chunk(lane, oct & 1);
   const size_t row_bytes = (size_t)D * 2;
   const char* dbase = (const char*)a.xb;
   uint32_t voff[4], qvoff[4];
@@ -793,7 +757,7 @@ __global__ __launch_bounds__(512) void flat_scan_wide_rs_kernel(const ScanArgs a
         constexpr int qb = decltype(qi)::value;
         if constexpr (f == 0) lgkm_wait<issued - 1 - (1 + qb)>();     // B0[qb] is read 1 + qb
         else if constexpr (qb == 0) lgkm_wait<issued - 1 - need>();    // (the B fragments of the fragment's k slice are covered by `need`)
-        Mfma16Fixed128<T>::template run<4 * ((2 * t + rb) * 4 + qb), FIRST && par == 0>(c[f % NB], bq[par][qb]);
+        Mfma16Fixed<T, 128>::template run<4 * ((2 * t + rb) * 4 + qb), FIRST && par == 0>(c[f % NB], bq[par][qb]);
       });
       if constexpr (f < 4) read_b(std::integral_constant<int, 1>{}, std::integral_constant<int, f>{});
       if constexpr (f + AH < NF) read_a(std::integral_constant<int, f + AH>{});
@@ -821,23 +785,10 @@ __global__ __launch_bounds__(512) void flat_scan_wide_rs_kernel(const ScanArgs a
         f32x4 e[2][4];
         static_for<4>([&](auto qi) {
           constexpr int qb = decltype(qi)::value;
-          e[0][qb] = read_acc_fixed128<4 * ((2 * t) * 4 + qb)>();
-          e[1][qb] = read_acc_fixed128<4 * ((2 * t + 1) * 4 + qb)>();
+          e[0][qb] = read_acc_fixed<128, 4 * ((2 * t) * 4 + qb)>();
+          e[1][qb] = read_acc_fixed<128, 4 * ((2 * t + 1) * 4 + qb)>();
         });
-        if (L2) {
-          const uint32_t r0 = (a.tile_first + j * a.tile_stride) * kTileRows + 4 * g;
-          f32x4 h0, h1;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            h0[i] = a.half_sqnorm[r0 + i < a.n_rows ? r0 + i : a.n_rows - 1];
-            h1[i] = a.half_sqnorm[r0 + 16 + i < a.n_rows ? r0 + 16 + i : a.n_rows - 1];
-          }
-#pragma unroll
-          for (int qb = 0; qb < 4; ++qb) {
-            e[0][qb] -= h0;
-            e[1][qb] -= h1;
-          }
-        }
+        if (L2) subtract_half_sqnorms<4>(a, j, g, e);
         tile_epilogue16<false, 4, 64, true, 8>(a, st, e, j, lane, wave, qq);
       }
     });
@@ -902,40 +853,17 @@ static hipError_t launch_scan_wide_t(const ScanArgs& a, int D, bool dense, int g
   const bool one8 = a.nq <= 64;                            // eight-wave kernel: 1 block per wave up to 64 queries (measured at d = 2048,
                                                            // 128 queries: 2 blocks on four waves 0.76, 1 block on eight 0.73 - every LDS
                                                            // fragment read then feeds one MFMA instead of two)
-  hipError_t e;
-#define RR_LAUNCH_KERNEL(...)                                                                                        \
-  {                                                                                                                  \
-    e = hipFuncSetAttribute((const void*)__VA_ARGS__, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);        \
-    if (e != hipSuccess) return e;                                                                                   \
-    hipLaunchKernelGGL((__VA_ARGS__), dim3(grid), dim3(256), lds, st, a, D);                                        \
-    return hipGetLastError();                                                                                        \
-  }
-#define RR_LAUNCH_PD(DENSE_, L2_, NQB_) RR_LAUNCH_KERNEL(flat_scan_wide_pd_kernel<T, DENSE_, L2_, NQB_>)
+#define RR_LAUNCH_PD(DENSE_, L2_, NQB_) return launch_with_lds(flat_scan_wide_pd_kernel<T, DENSE_, L2_, NQB_>, grid, 256, lds, st, a, D);
   if (!dense && scan_wide_rowsplit(D, (int)a.nq, l2, a.k)) {
     const size_t lds_rs = (size_t)5 * 8 * 4096;   // 3 corpus + 2 query slots of 32 KB: all 160 KB
     if (l2 && a.ranges) return hipErrorNotSupported;
-#define RR_LAUNCH_RS(...)                                                                                            \
-  {                                                                                                                  \
-    hipError_t ers = hipFuncSetAttribute((const void*)__VA_ARGS__, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rs); \
-    if (ers != hipSuccess) return ers;                                                                               \
-    hipLaunchKernelGGL((__VA_ARGS__), dim3(grid), dim3(512), lds_rs, st, a, D);                                     \
-    return hipGetLastError();                                                                                        \
-  }
-    if (l2) RR_LAUNCH_RS(flat_scan_wide_rs_kernel<T, true>)
-    RR_LAUNCH_RS(flat_scan_wide_rs_kernel<T, false>)
-#undef RR_LAUNCH_RS
+    if (l2) return launch_with_lds(flat_scan_wide_rs_kernel<T, true>, grid, 512, lds_rs, st, a, D);
+    return launch_with_lds(flat_scan_wide_rs_kernel<T, false>, grid, 512, lds_rs, st, a, D);
   }
   if (!dense && wide_waves_for(D, (int)a.nq) == 8) {
-    hipError_t e8;
-#define RR_LAUNCH_8(...)                                                                                             \
-  {                                                                                                                  \
-    e8 = hipFuncSetAttribute((const void*)__VA_ARGS__, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);       \
-    if (e8 != hipSuccess) return e8;                                                                                 \
-    hipLaunchKernelGGL((__VA_ARGS__), dim3(grid), dim3(512), lds, st, a, D);                                        \
-    return hipGetLastError();                                                                                        \
-  }
-    if (l2) { if (one8) RR_LAUNCH_8(flat_scan_wide8_kernel<T, true, 1>) else RR_LAUNCH_8(flat_scan_wide8_kernel<T, true, 2>) }
-    if (one8) RR_LAUNCH_8(flat_scan_wide8_kernel<T, false, 1>) else RR_LAUNCH_8(flat_scan_wide8_kernel<T, false, 2>)
+#define RR_LAUNCH_8(L2_, NQB_) return launch_with_lds(flat_scan_wide8_kernel<T, L2_, NQB_>, grid, 512, lds, st, a, D);
+    if (l2) { if (one8) RR_LAUNCH_8(true, 1) else RR_LAUNCH_8(true, 2) }
+    if (one8) RR_LAUNCH_8(false, 1) else RR_LAUNCH_8(false, 2)
 #undef RR_LAUNCH_8
   }
 #define RR_LAUNCH_PD_N(DENSE_, L2_)                      \
@@ -953,7 +881,6 @@ static hipError_t launch_scan_wide_t(const ScanArgs& a, int D, bool dense, int g
   RR_LAUNCH_PD_N(false, false)
 #undef RR_LAUNCH_PD_N
 #undef RR_LAUNCH_PD
-#undef RR_LAUNCH_KERNEL
 }
 
 hipError_t launch_scan_wide(const ScanArgs& a, int dtype, int D, bool dense, int grid, hipStream_t st) {
