@@ -18,7 +18,8 @@ int fail(int code, const char* fmt, const char* detail = "") {
   snprintf(g_err, sizeof(g_err), fmt, detail);
   return code;
 }
-int hip_fail(hipError_t e, const char* where) {
+int hip_status(hipError_t e, const char* where) {   // RR_OK, or RR_ERR_HIP with "where: what HIP says" recorded
+  if (e == hipSuccess) return RR_OK;
   snprintf(g_err, sizeof(g_err), "%s: %s", where, hipGetErrorString(e));
   return RR_ERR_HIP;
 }
@@ -41,37 +42,38 @@ struct ProfEntry { hipEvent_t start, stop; uint64_t rows; };
 thread_local ProfEntry* g_prof = nullptr;
 thread_local int g_prof_cap = 0, g_prof_n = 0, g_prof_dropped = 0;
 
-hipError_t profiled_scan(const rr::ScanArgs& a, int dtype, int D, bool dense, int grid, hipStream_t st) {
-  if (g_prof && g_prof_n >= g_prof_cap) ++g_prof_dropped;   // rr_profile_end reports it: a silent drop would overstate the roofline
-  if (g_prof && g_prof_n < g_prof_cap) {
-    ProfEntry& p = g_prof[g_prof_n++];
-    p.rows = (uint64_t)a.n_tiles * rr::kTileRows;
-    (void)hipEventRecord(p.start, st);
-    hipError_t e = rr::launch_flat_scan(a, dtype, D, dense, grid, st);
-    (void)hipEventRecord(p.stop, st);
-    return e;
-  }
-  return rr::launch_flat_scan(a, dtype, D, dense, grid, st);
+hipError_t profiled_scan(const rr::ScanArgs& a, const rr::ScanPlan& plan, bool dense, int grid, hipStream_t st) {
+  ProfEntry* p = g_prof && g_prof_n < g_prof_cap ? &g_prof[g_prof_n++] : nullptr;
+  if (g_prof && !p) ++g_prof_dropped;   // rr_profile_end reports it: a silent drop would overstate the roofline
+  if (p) { p->rows = (uint64_t)a.n_tiles * rr::kTileRows; (void)hipEventRecord(p->start, st); }
+  const hipError_t e = rr::launch_flat_scan(a, plan, dense, grid, st);
+  if (p) (void)hipEventRecord(p->stop, st);
+  return e;
 }
 
 // Schedule knobs (defaults from rr_common.h; RR_SAMPLE_ROWS / RR_CHUNK_GROWTH override them for tuning runs)
-int g_sample_rows = rr::kSampleRows, g_chunk_growth = 0;  // 0 = size-aware schedule
-void read_schedule_env() {
-  static const bool once = [] {
-    if (const char* v = rr::tuning_env("RR_SAMPLE_ROWS")) {
-      int r = atoi(v) / rr::kTileRows * rr::kTileRows;
-      if (r >= 1024 && r <= rr::kSampleRows) g_sample_rows = r;
-    }
-    if (const char* v = rr::tuning_env("RR_CHUNK_GROWTH")) {
-      int g = atoi(v);
-      if (g >= 2 && g <= 1024) g_chunk_growth = g;
-    }
-    return true;
+int sample_rows() {
+  static const int v = [] {
+    const char* e = rr::tuning_env("RR_SAMPLE_ROWS");
+    const int r = e ? atoi(e) / rr::kTileRows * rr::kTileRows : 0;
+    return r >= 1024 && r <= rr::kSampleRows ? r : rr::kSampleRows;
   }();
-  (void)once;
+  return v;
+}
+int chunk_growth() {   // 0 = the size-aware schedule
+  static const int v = [] { const char* e = rr::tuning_env("RR_CHUNK_GROWTH"); const int g = e ? atoi(e) : 0; return g >= 2 && g <= 1024 ? g : 0; }();
+  return v;
 }
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+struct Bump {   // bump allocator of the workspace layouts: 256-byte aligned pieces; base == nullptr only measures
+  char* base;
+  size_t off = 0;
+  template <typename T> T* take(size_t count) {
+    const size_t o = off;
+    off = (off + count * sizeof(T) + 255) / 256 * 256;
+    return base ? (T*)(base + o) : nullptr;
+  }
+};
 
 // Growth factor of the chunk schedule for a shard that is `ratio` times the bootstrap sample.  With c chunks the growth is
 // g = ratio^(1/c) and every chunk leaves ~(g - 1) k survivors per query.  A workgroup sees every query, so it takes the
@@ -80,7 +82,7 @@ size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // for the launch's fixed part and its compaction, ~0.18 us per insertion event of a workgroup.
 // 1M x 768, k = 32 -> 3 chunks; 10M -> 4; 80M at k = 100 -> 6.
 double chunk_schedule(double ratio, int k) {
-  if (g_chunk_growth > 0) return (double)g_chunk_growth;   // RR_CHUNK_GROWTH pins the round-1 schedule for A/B runs
+  if (chunk_growth() > 0) return (double)chunk_growth();   // RR_CHUNK_GROWTH pins the round-1 schedule for A/B runs
   if (ratio <= 1.0) return 2.0;
   double best_cost = 1e30, best_g = 8.0;
   for (int c = 1; c <= 8; ++c) {
@@ -95,41 +97,195 @@ struct Workspace {
   uint32_t *seg_tile_end, *seg_row_limit, *seg_row_begin, *seg_sel;   // segmented search: device tables written by prep_kernel
   int64_t* seg_id_offset;
   rr::RangeEntry* ranges;                                             // [kMaxChunks][kMaxSegments] tile runs of the chunk launches
-  float* thr;
-  uint32_t* list_cnt;
-  uint64_t* list;
-  uint32_t* cand_cnt;
-  uint64_t* scratch;
-  float* dense;
-  uint64_t* cand;
+  float *thr, *dense;
+  uint32_t *list_cnt, *cand_cnt;
+  uint64_t *list, *scratch, *cand;
   void* xqs;
   size_t total;
 };
 
-Workspace carve(char* base, int k, int grid, int dim) {
+Workspace carve(char* base, int k, int grid, int dtype, int dim) {
   using namespace rr;
-  const int cap = cand_cap_for_k(k);
-  // candidate buffers per (workgroup, query): 4 lane quarters; the row-split wide-row kernel (dim > 768) uses 8
-  const int bpw = dim > kMaxResidentDim ? 8 : 4;
+  const size_t cap = cand_cap_for_k(k), nq = kQueriesPerBlock;
+  const size_t nbuf = (size_t)grid * scan_max_bufs_per_wg(dtype, dim);   // candidate buffers per query of the widest plan at this dim
   Workspace w;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return base ? base + o : (char*)nullptr; };
-  w.thr = (float*)take((size_t)kMaxSegments * kQueriesPerBlock * sizeof(float));   // [segment][query] (plain search: row 0)
-  w.seg_tile_end = (uint32_t*)take(kMaxSegments * sizeof(uint32_t));
-  w.seg_row_limit = (uint32_t*)take(kMaxSegments * sizeof(uint32_t));
-  w.seg_row_begin = (uint32_t*)take(kMaxSegments * sizeof(uint32_t));
-  w.seg_id_offset = (int64_t*)take(kMaxSegments * sizeof(int64_t));
-  w.seg_sel = (uint32_t*)take(kQueriesPerBlock * sizeof(uint32_t));
-  w.ranges = (RangeEntry*)take((size_t)kMaxChunks * kMaxSegments * sizeof(RangeEntry));
-  w.list_cnt = (uint32_t*)take(kQueriesPerBlock * sizeof(uint32_t));
-  w.list = (uint64_t*)take((size_t)kQueriesPerBlock * kMaxK * sizeof(uint64_t));
-  w.cand_cnt = (uint32_t*)take((size_t)kQueriesPerBlock * grid * bpw * sizeof(uint32_t));
-  w.scratch = (uint64_t*)take((size_t)grid * 8 * cap * sizeof(uint64_t));  // up to 2 workgroups per CU x 4 waves
-  w.dense = (float*)take((size_t)kQueriesPerBlock * kSampleRows * sizeof(float));
-  w.cand = (uint64_t*)take((size_t)kQueriesPerBlock * grid * bpw * cap * sizeof(uint64_t));
-  w.xqs = take((size_t)kQueriesPerBlock * kMaxDim * 2);  // the query block in MFMA-fragment order (prep kernel): 256 queries x the padded dim
-  w.total = off;
+  Bump b{base};
+  w.thr = b.take<float>(kMaxSegments * nq);   // [segment][query] (plain search: row 0)
+  w.seg_tile_end = b.take<uint32_t>(kMaxSegments);
+  w.seg_row_limit = b.take<uint32_t>(kMaxSegments);
+  w.seg_row_begin = b.take<uint32_t>(kMaxSegments);
+  w.seg_id_offset = b.take<int64_t>(kMaxSegments);
+  w.seg_sel = b.take<uint32_t>(nq);
+  w.ranges = b.take<RangeEntry>((size_t)kMaxChunks * kMaxSegments);
+  w.list_cnt = b.take<uint32_t>(nq);
+  w.list = b.take<uint64_t>(nq * kMaxK);
+  w.cand_cnt = b.take<uint32_t>(nq * nbuf);
+  w.scratch = b.take<uint64_t>((size_t)grid * 8 * cap);  // up to 2 workgroups per CU x 4 waves
+  w.dense = b.take<float>(nq * kSampleRows);
+  w.cand = b.take<uint64_t>(nq * nbuf * cap);
+  w.xqs = b.take<char>(nq * kMaxDim * 2);  // the query block in MFMA-fragment order (prep kernel): 256 queries x the padded dim
+  w.total = b.off;
   return w;
+}
+
+// ---- the schedule of one search ---------------------------------------------------------------------------------------------------
+// One scan launch of the chunk schedule and the compaction behind it.  Plain search: tiles [tile_first, tile_first + n_tiles).
+// Segmented: chunk `index` of the range tables prep_kernel writes, n_tiles launch ordinals in n_ranges runs; n_tiles == 0 (only the
+// last chunk may be empty) compacts without a scan.
+struct Chunk { uint32_t tile_first, n_tiles, index, n_ranges; };
+// growth >= 1.5 from a sample of >= 32 tiles up to < 2^27 tiles: at most 38 chunks (product builds: chunk_schedule picks <= 8)
+constexpr uint32_t kMaxPlainChunks = 40;
+// The launches of a search as far as they depend on the corpus and the segments alone: computed once per call, run per query block.
+struct Schedule { uint32_t total_tiles, n_sample_tiles, n_chunks; Chunk chunks[kMaxPlainChunks]; };
+
+// Plain schedule: chunks [0,e1), [e1,e2), ... with e growing geometrically: a chunk that is g times what came before it yields
+// ~(g-1) k survivors per query.  The number of chunks balances the fixed cost of a scan launch + compaction against the insertion
+// work of a long chunk (chunk_schedule).
+void plain_chunks(Schedule& sc, double growth) {
+  uint64_t begin = 0;
+  double endf = (double)sc.n_sample_tiles * growth;  // in tiles
+  while (begin < sc.total_tiles) {
+    uint64_t end = ((uint64_t)(endf + 0.5) + 7) & ~7ull;   // whole 256-row groups: the wide-row kernels' K order is a function of the global group (flat_scan_wide.hip)
+    if (end > sc.total_tiles || (double)sc.total_tiles < endf * 1.25) end = sc.total_tiles;  // no sliver of a last chunk
+    if (end <= begin) end = begin + 8;
+    if (end > sc.total_tiles || sc.n_chunks + 1 == kMaxPlainChunks) end = sc.total_tiles;
+    sc.chunks[sc.n_chunks++] = Chunk{(uint32_t)begin, (uint32_t)(end - begin), 0, 0};
+    begin = end;
+    endf *= growth;
+  }
+}
+
+// Segmented schedule: chunk c takes the next slice of EVERY segment (seg_cut), reaching the cumulative fraction frac[c] of each, so
+// that whatever subset of the segments a query is routed to, its rows arrive in geometrically growing portions.  frac[c] = sample
+// share x growth^(c+1), the last one 1 (no sliver of a last chunk).  The launch sizes here and prep_kernel's range tables (from the
+// same SegHost) use one expression.  A chunk that is empty in every segment is dropped, except the last: its compaction finalizes.
+void segment_chunks(Schedule& sc, rr::SegHost& segs, double ratio, double growth) {
+  using namespace rr;
+  double f = growth / ratio;
+  uint32_t nc = 0;
+  for (; nc + 1 < (uint32_t)kMaxChunks && f * 1.25 < 1.0; ++nc, f *= growth) segs.frac[nc] = (uint32_t)(f * 4294967296.0);
+  segs.frac[nc++] = 0xFFFFFFFFu;
+  segs.n_chunks = nc;
+  for (uint32_t c = 0; c < nc; ++c) {
+    Chunk ch{0, 0, c, 0};
+    for (uint32_t sg = 0; sg < segs.n; ++sg) {
+      const uint32_t tiles = (segs.row_limit[sg] - segs.row_begin[sg] + kTileRows - 1) / kTileRows;
+      const uint32_t lo = c ? seg_cut(tiles, segs.frac[c - 1]) : 0u, hi = seg_cut(tiles, segs.frac[c]);
+      if (hi > lo) { ch.n_tiles += (hi - lo + 7u) & ~7u; ++ch.n_ranges; }
+    }
+    if (ch.n_tiles > 0 || c + 1 == nc) sc.chunks[sc.n_chunks++] = ch;
+  }
+}
+
+// What the launches of one block of queries share.
+struct Block { rr::ScanPlan plan; rr::SelectArgs s; rr::ScanArgs a; int grid; hipStream_t st; };
+
+// All scores of n_tiles tiles, every tile_stride-th one of the corpus, and one exact selection from them.
+int dense_pass(Block& b, uint32_t tile_stride, uint32_t n_tiles, bool bootstrap) {
+  b.a.tile_first = 0; b.a.tile_stride = tile_stride; b.a.n_tiles = n_tiles;
+  if (int rc = hip_status(profiled_scan(b.a, b.plan, true, b.grid, b.st), bootstrap ? "rr_flat_search/bootstrap" : "rr_flat_search/dense")) return rc;
+  b.s.tile_first = 0; b.s.tile_stride = tile_stride; b.s.dense_cols = n_tiles * rr::kTileRows;
+  return hip_status(rr::launch_dense_select(b.s, bootstrap, b.st), bootstrap ? "rr_flat_search/bootstrap_select" : "rr_flat_search/dense_select");
+}
+// tiny corpus: every row
+int schedule_dense(Block& b, const Schedule& sc) { return dense_pass(b, 1, sc.total_tiles, false); }
+// head of both chunk schedules: the k-th best score of a strided sample of tiles = a valid lower bound
+int bootstrap(Block& b, const Schedule& sc) { return dense_pass(b, sc.total_tiles / sc.n_sample_tiles, sc.n_sample_tiles, true); }
+
+// bootstrap, then scan + compaction per chunk.  fin != nullptr: the last compaction emits (D, I).
+int schedule_chunks(Block& b, const Schedule& sc, const rr::FinalizeArgs* fin) {
+  if (int rc = bootstrap(b, sc)) return rc;
+  b.a.tile_stride = 1;
+  b.a.timeline = rr::tuning_env("RR_SCAN_TIMELINE") ? (uint64_t*)b.a.dense : nullptr;  // the dense buffer is idle during chunk scans
+  for (uint32_t i = 0; i < sc.n_chunks; ++i) {
+    b.a.tile_first = sc.chunks[i].tile_first; b.a.n_tiles = sc.chunks[i].n_tiles;
+    if (int rc = hip_status(profiled_scan(b.a, b.plan, false, b.grid, b.st), "rr_flat_search/scan")) return rc;
+    if (int rc = hip_status(rr::launch_compact(b.s, i + 1 == sc.n_chunks ? fin : nullptr, b.st), "rr_flat_search/compact")) return rc;
+  }
+  return RR_OK;
+}
+
+// the same over the range tables (device [kMaxChunks][kMaxSegments], written by prep_kernel)
+int schedule_segment_chunks(Block& b, const Schedule& sc, const rr::RangeEntry* ranges, const rr::FinalizeArgs* fin) {
+  if (int rc = bootstrap(b, sc)) return rc;
+  b.a.tile_first = 0; b.a.tile_stride = 1;
+  for (uint32_t i = 0; i < sc.n_chunks; ++i) {
+    const Chunk& c = sc.chunks[i];
+    b.a.n_tiles = c.n_tiles; b.a.ranges = ranges + (size_t)c.index * rr::kMaxSegments; b.a.n_ranges = c.n_ranges;
+    if (c.n_tiles > 0)
+      if (int rc = hip_status(profiled_scan(b.a, b.plan, false, b.grid, b.st), "rr_flat_search_segments/scan")) return rc;
+    if (int rc = hip_status(rr::launch_compact(b.s, i + 1 == sc.n_chunks ? fin : nullptr, b.st), "rr_flat_search_segments/compact")) return rc;
+  }
+  return RR_OK;
+}
+
+// segs != nullptr: segmented search — xb is ONE matrix of n_rows rows holding several sources (segs->row_begin / row_limit),
+// scanned as one corpus; route_mask then is [nq][mask_stride] with one column per segment (segs->mask_col), id_offset unused.
+int flat_search_impl(const void* xb, int dtype, int64_t n_rows, int dim, const void* xq, int nq, int k, float* D, int64_t* I,
+                     int64_t id_offset, void* ws, size_t ws_bytes, const uint8_t* route_mask, int64_t mask_stride,
+                     const float* half_sqnorm, void* stream, rr::SegHost* segs = nullptr) {
+  using namespace rr;
+  hipStream_t st = (hipStream_t)stream;
+  if (k < 1 || k > kMaxK) return fail(RR_ERR_INVALID, "rr_flat_search: k must be in [1, 1024]%s");
+  if (nq < 0 || n_rows < 0) return fail(RR_ERR_INVALID, "rr_flat_search: negative size%s");
+  if (n_rows > 0xFFFFFFE0ll) return fail(RR_ERR_UNSUPPORTED, "rr_flat_search: more than 2^32-32 rows per shard%s");
+  if (!half_dtype(dtype) && dtype != kDtypeI8) return fail(RR_ERR_INVALID, "rr_flat_search: bad dtype%s");
+  if (scan_padded_dim(dim) != dim) return fail(RR_ERR_UNSUPPORTED, "rr_flat_search: dim must equal rr_padded_dim(d)%s");
+  if (nq == 0) return RR_OK;
+  if (!xq || !D || !I || !ws || (!xb && n_rows > 0)) return fail(RR_ERR_INVALID, "rr_flat_search: null pointer%s");
+  const int grid = device_cus();
+  if (grid <= 0) return fail(RR_ERR_HIP, "rr_flat_search: no HIP device%s");
+  const Workspace w = carve((char*)ws, k, grid, dtype, dim);
+  if (ws_bytes < w.total) return fail(RR_ERR_WORKSPACE, "rr_flat_search: workspace smaller than rr_flat_search_workspace_bytes_for(k, dim)%s");
+
+  const bool l2 = half_sqnorm != nullptr, chunked = n_rows > kDenseMaxRows;   // (up to kDenseMaxRows rows: the dense schedule)
+  // THE decision on who writes (D, I): the last compaction of an inner-product chunk schedule does; every other search - L2, tiny or
+  // empty corpus - ends with launch_finalize
+  const bool compact_finalizes = chunked && !l2;
+  Schedule sc{(uint32_t)((n_rows + kTileRows - 1) / kTileRows), (uint32_t)sample_rows() / kTileRows, 0, {}};
+  if (chunked) {
+    const double ratio = (double)sc.total_tiles / sc.n_sample_tiles, growth = chunk_schedule(ratio, k);
+    if (segs) { segment_chunks(sc, *segs, ratio, growth); segs->ranges = w.ranges; }
+    else plain_chunks(sc, growth);
+  }
+
+  const int cap = cand_cap_for_k(k);
+  const int qpl = scan_queries_per_launch(dim, nq);  // 256, or 128 where only 32 queries per wave stay resident and the batch is small
+  for (int qb = 0; qb < nq; qb += qpl) {
+    const int nqb = nq - qb < qpl ? nq - qb : qpl;
+    const char* xq_b = (const char*)xq + (size_t)qb * dim * 2;
+    // (segmented: the per-query route mask rows of this query block are folded into the thresholds by prep, not into the finalize)
+    const uint8_t* mask_b = route_mask ? route_mask + (size_t)qb * mask_stride : nullptr;
+    const FinalizeArgs fin{D + (size_t)qb * k, I + (size_t)qb * k, id_offset, segs ? nullptr : mask_b, mask_stride};
+
+    Block b;
+    memset(&b, 0, sizeof(b));
+    // (per query block: the kernel is picked from the block's own query count, e.g. the 44-query tail of a 300-query call)
+    b.plan = scan_plan(dtype, dim, nqb, l2);
+    b.grid = grid; b.st = st;
+    SelectArgs& s = b.s;
+    s.thr = w.thr; s.list = w.list; s.list_cnt = w.list_cnt; s.cand = w.cand; s.cand_cnt = w.cand_cnt;
+    s.dense = w.dense; s.dense_ld = kSampleRows; s.n_rows = (uint32_t)n_rows; s.nq = (uint32_t)nqb;
+    s.nbuf = (uint32_t)grid * (uint32_t)b.plan.bufs_per_wg; s.list_ld = kMaxK; s.cap = cap; s.k = k;
+    if (segs) s.seg = SegTables{w.seg_tile_end, w.seg_row_limit, w.seg_row_begin, w.seg_id_offset, w.seg_sel, segs->n};
+    ScanArgs& a = b.a;
+    a.xb = xb; a.xq = xq_b; a.xqs = w.xqs; a.thr = w.thr; a.cand = w.cand; a.cand_cnt = w.cand_cnt; a.scratch = w.scratch;
+    a.dense = w.dense; a.n_rows = (uint32_t)n_rows; a.nq = (uint32_t)nqb; a.dense_ld = kSampleRows; a.cap = cap; a.k = k;
+    a.half_sqnorm = half_sqnorm;
+    if (segs) a.ties_pass = 1;
+
+    if (int rc = hip_status(launch_prep(s, xq_b, w.xqs, dim, b.plan.blocks_per_wave, st, segs, segs ? mask_b : nullptr, mask_stride),
+                            "rr_flat_search/prep")) return rc;
+    const FinalizeArgs* cfin = compact_finalizes ? &fin : nullptr;
+    int rc = RR_OK;
+    if (chunked) rc = segs ? schedule_segment_chunks(b, sc, w.ranges, cfin) : schedule_chunks(b, sc, cfin);
+    else if (n_rows > 0) rc = schedule_dense(b, sc);
+    if (rc != RR_OK) return rc;
+    if (compact_finalizes) continue;
+    if (int rc = hip_status(launch_finalize(s, fin.D, fin.I, fin.id_offset, fin.mask, fin.mask_stride, l2 ? (const void*)xq_b : nullptr,
+                                            dtype, dim, st), "rr_flat_search/finalize")) return rc;
+  }
+  return RR_OK;
 }
 
 }  // namespace
@@ -160,175 +316,35 @@ int rr_padded_dim(int d) {
 
 int rr_l2_normalize_f32(float* x, int64_t n, int64_t d, void* stream) {
   if (n < 0 || d <= 0 || (!x && n > 0)) return fail(RR_ERR_INVALID, "rr_l2_normalize_f32: bad arguments%s");
-  hipError_t e = rr::launch_l2_normalize_f32(x, n, d, (hipStream_t)stream);
-  return e == hipSuccess ? RR_OK : hip_fail(e, "rr_l2_normalize_f32");
+  return hip_status(rr::launch_l2_normalize_f32(x, n, d, (hipStream_t)stream), "rr_l2_normalize_f32");
 }
 
 int rr_rows_to_half(const float* x, int64_t n, int64_t d, int64_t ld_in, void* out, int dtype, int64_t d_out,
                     int normalize, void* stream) {
   if (n < 0 || d <= 0 || ld_in < d || d_out < d || ((!x || !out) && n > 0))
     return fail(RR_ERR_INVALID, "rr_rows_to_half: bad arguments%s");
-  if (dtype != RR_DTYPE_F16 && dtype != RR_DTYPE_BF16) return fail(RR_ERR_INVALID, "rr_rows_to_half: bad dtype%s");
-  hipError_t e = rr::launch_rows_to_half(x, n, d, ld_in, out, dtype, d_out, normalize, (hipStream_t)stream);
-  return e == hipSuccess ? RR_OK : hip_fail(e, "rr_rows_to_half");
+  if (!rr::half_dtype(dtype)) return fail(RR_ERR_INVALID, "rr_rows_to_half: bad dtype%s");
+  return hip_status(rr::launch_rows_to_half(x, n, d, ld_in, out, dtype, d_out, normalize, (hipStream_t)stream), "rr_rows_to_half");
 }
 
 int rr_centroid(const void* xb, int dtype, int64_t n_rows, int dim, int d, float* out, void* stream) {
   if (n_rows < 0 || d < 1 || d > dim || dim % 64 != 0 || !out || (!xb && n_rows > 0))
     return fail(RR_ERR_INVALID, "rr_centroid: bad arguments%s");
-  if (dtype != RR_DTYPE_F16 && dtype != RR_DTYPE_BF16) return fail(RR_ERR_INVALID, "rr_centroid: bad dtype%s");
-  hipError_t e = rr::launch_centroid(xb, dtype, n_rows, dim, d, out, (hipStream_t)stream);
-  return e == hipSuccess ? RR_OK : hip_fail(e, "rr_centroid");
+  if (!rr::half_dtype(dtype)) return fail(RR_ERR_INVALID, "rr_centroid: bad dtype%s");
+  return hip_status(rr::launch_centroid(xb, dtype, n_rows, dim, d, out, (hipStream_t)stream), "rr_centroid");
 }
 
-size_t rr_flat_search_workspace_bytes(int k) {   // any dim
-  if (k < 1 || k > rr::kMaxK) return 0;
-  int grid = device_cus();
-  if (grid <= 0) return 0;
-  return carve(nullptr, k, grid, rr::kMaxDim).total;
-}
+size_t rr_flat_search_workspace_bytes(int k) { return rr_flat_search_workspace_bytes_for(k, rr::kMaxDim); }   // any dim
 size_t rr_flat_search_workspace_bytes_for(int k, int dim) {
   if (k < 1 || k > rr::kMaxK || rr::scan_padded_dim(dim) != dim) return 0;
-  int grid = device_cus();
-  if (grid <= 0) return 0;
-  return carve(nullptr, k, grid, dim).total;
-}
-
-// segs != nullptr: segmented search — xb is ONE matrix of n_rows rows holding several sources (segs->row_begin / row_limit),
-// scanned as one corpus; route_mask then is [nq][mask_stride] with one column per segment (segs->mask_col), id_offset unused.
-static int flat_search_impl(const void* xb, int dtype, int64_t n_rows, int dim, const void* xq, int nq, int k, float* D,
-                            int64_t* I, int64_t id_offset, void* ws, size_t ws_bytes, const uint8_t* route_mask,
-                            int64_t mask_stride, const float* half_sqnorm, void* stream, rr::SegHost* segs = nullptr) {
-  using namespace rr;
-  hipStream_t st = (hipStream_t)stream;
-  if (k < 1 || k > kMaxK) return fail(RR_ERR_INVALID, "rr_flat_search: k must be in [1, 1024]%s");
-  if (nq < 0 || n_rows < 0) return fail(RR_ERR_INVALID, "rr_flat_search: negative size%s");
-  if (n_rows > 0xFFFFFFE0ll) return fail(RR_ERR_UNSUPPORTED, "rr_flat_search: more than 2^32-32 rows per shard%s");
-  if (dtype != RR_DTYPE_F16 && dtype != RR_DTYPE_BF16 && dtype != kDtypeI8) return fail(RR_ERR_INVALID, "rr_flat_search: bad dtype%s");
-  if (scan_padded_dim(dim) != dim)
-    return fail(RR_ERR_UNSUPPORTED, "rr_flat_search: dim must equal rr_padded_dim(d)%s");
-  if (nq == 0) return RR_OK;
-  if (!xq || !D || !I || !ws || (!xb && n_rows > 0)) return fail(RR_ERR_INVALID, "rr_flat_search: null pointer%s");
   const int grid = device_cus();
-  if (grid <= 0) return fail(RR_ERR_HIP, "rr_flat_search: no HIP device%s");
-  Workspace w = carve((char*)ws, k, grid, dtype == kDtypeI8 ? kMaxResidentDim : dim);
-  if (ws_bytes < w.total) return fail(RR_ERR_WORKSPACE, "rr_flat_search: workspace smaller than rr_flat_search_workspace_bytes_for(k, dim)%s");
-
-  read_schedule_env();
-  const int cap = cand_cap_for_k(k);
-  const uint32_t total_tiles = (uint32_t)((n_rows + kTileRows - 1) / kTileRows);
-  hipError_t e;
-#define RR_CHECK(call, what) do { e = (call); if (e != hipSuccess) return hip_fail(e, what); } while (0)
-
-  if (segs && n_rows > kDenseMaxRows) {
-    // chunk fractions of the segmented schedule: frac[c] = sample share x growth^(c+1), the last one 1 (no sliver of a last chunk)
-    const uint32_t n_sample_tiles = (uint32_t)g_sample_rows / kTileRows;
-    const double ratio = (double)total_tiles / n_sample_tiles, growth = chunk_schedule(ratio, k);
-    double f = growth / ratio;
-    uint32_t c = 0;
-    for (; c + 1 < (uint32_t)kMaxChunks && f * 1.25 < 1.0; ++c, f *= growth) segs->frac[c] = (uint32_t)(f * 4294967296.0);
-    segs->frac[c++] = 0xFFFFFFFFu;
-    segs->n_chunks = c;
-    segs->ranges = w.ranges;
-  }
-  const int qpl = scan_queries_per_launch(dim, nq);  // 256, or 128 where only 32 queries per wave stay resident and the batch is small
-  for (int qb = 0; qb < nq; qb += qpl) {
-    const int nqb = nq - qb < qpl ? nq - qb : qpl;
-    const char* xq_b = (const char*)xq + (size_t)qb * dim * 2;
-    float* D_b = D + (size_t)qb * k;
-    int64_t* I_b = I + (size_t)qb * k;
-
-    SelectArgs s;
-    memset(&s, 0, sizeof(s));
-    s.thr = w.thr; s.list = w.list; s.list_cnt = w.list_cnt; s.cand = w.cand; s.cand_cnt = w.cand_cnt;
-    s.dense = w.dense; s.dense_ld = kSampleRows; s.n_rows = (uint32_t)n_rows; s.nq = (uint32_t)nqb;
-    s.nbuf = (uint32_t)grid * (uint32_t)(dtype == kDtypeI8 ? 4 : scan_bufs_per_wg(dim, nqb, half_sqnorm != nullptr, k)); s.list_ld = kMaxK; s.cap = cap; s.k = k;
-    if (segs) s.seg = SegTables{w.seg_tile_end, w.seg_row_limit, w.seg_row_begin, w.seg_id_offset, w.seg_sel, segs->n};
-    ScanArgs a;
-    memset(&a, 0, sizeof(a));
-    a.xb = xb; a.xq = xq_b; a.thr = w.thr; a.cand = w.cand; a.cand_cnt = w.cand_cnt; a.scratch = w.scratch;
-    a.dense = w.dense; a.n_rows = (uint32_t)n_rows; a.nq = (uint32_t)nqb; a.dense_ld = kSampleRows; a.cap = cap; a.k = k;
-    a.half_sqnorm = half_sqnorm;
-    if (segs) a.ties_pass = 1;
-    // (per query block: launch_flat_scan picks the kernel from the block's own query count, e.g. the 44-query tail of a 300-query call)
-    const int bpw = dtype == kDtypeI8 ? 4 : scan_query_blocks_per_wave(dim, nqb, half_sqnorm != nullptr);
-    a.xqs = bpw ? w.xqs : nullptr;
-
-    bool finalized = false;
-    // (segmented: the per-query route mask rows of this query block; folded into the thresholds, not into the finalize)
-    const uint8_t* mask_b = route_mask ? route_mask + (size_t)qb * mask_stride : nullptr;
-    RR_CHECK(launch_prep(s, xq_b, w.xqs, dim, bpw, st, segs, segs ? mask_b : nullptr, mask_stride), "rr_flat_search/prep");
-    if (n_rows > 0 && n_rows <= kDenseMaxRows) {
-      // tiny corpus: all scores, one exact selection
-      a.tile_first = 0; a.tile_stride = 1; a.n_tiles = total_tiles;
-      RR_CHECK(profiled_scan(a, dtype, dim, true, grid, st), "rr_flat_search/dense");
-      s.tile_first = 0; s.tile_stride = 1; s.dense_cols = total_tiles * kTileRows;
-      RR_CHECK(launch_dense_select(s, false, st), "rr_flat_search/dense_select");
-    } else if (n_rows > 0) {
-      // bootstrap: k-th best score of a strided sample of tiles = a valid lower bound
-      const uint32_t n_sample_tiles = (uint32_t)g_sample_rows / kTileRows;
-      a.tile_first = 0; a.tile_stride = total_tiles / n_sample_tiles; a.n_tiles = n_sample_tiles;
-      RR_CHECK(profiled_scan(a, dtype, dim, true, grid, st), "rr_flat_search/bootstrap");
-      s.tile_first = 0; s.tile_stride = a.tile_stride; s.dense_cols = (uint32_t)g_sample_rows;
-      RR_CHECK(launch_dense_select(s, true, st), "rr_flat_search/bootstrap_select");
-      // chunks [0,e1), [e1,e2), ... with e growing geometrically: a chunk that is g times what came before it yields ~(g-1) k
-      // survivors per query.  The number of chunks balances the fixed cost of a scan launch + compaction against the
-      // insertion work of a long chunk (chunk_schedule).
-      const double growth = chunk_schedule((double)total_tiles / n_sample_tiles, k);
-      FinalizeArgs fin{D_b, I_b, id_offset, segs ? nullptr : mask_b, mask_stride};
-      if (segs) {
-        // Segmented: chunk c takes the next slice of EVERY segment (seg_cut), reaching the cumulative fraction frac[c] of each, so
-        // that whatever subset of the segments a query is routed to, its rows arrive in geometrically growing portions.  The
-        // launch sizes below and prep_kernel's range tables (already enqueued above with the same SegHost) use one expression.
-        for (uint32_t c = 0; c < segs->n_chunks; ++c) {
-          uint32_t n_launch_tiles = 0, n_ranges = 0;
-          for (uint32_t sg = 0; sg < segs->n; ++sg) {
-            const uint32_t tiles = (segs->row_limit[sg] - segs->row_begin[sg] + kTileRows - 1) / kTileRows;
-            const uint32_t lo = c ? seg_cut(tiles, segs->frac[c - 1]) : 0u, hi = seg_cut(tiles, segs->frac[c]);
-            if (hi > lo) { n_launch_tiles += (hi - lo + 7u) & ~7u; ++n_ranges; }
-          }
-          const bool last = c + 1 == segs->n_chunks;
-          if (n_launch_tiles == 0 && !last) continue;
-          if (n_launch_tiles > 0) {
-            a.tile_first = 0; a.tile_stride = 1; a.n_tiles = n_launch_tiles;
-            a.ranges = w.ranges + (size_t)c * kMaxSegments; a.n_ranges = n_ranges;
-            RR_CHECK(profiled_scan(a, dtype, dim, false, grid, st), "rr_flat_search_segments/scan");
-          }
-          RR_CHECK(launch_compact(s, last ? &fin : nullptr, st), "rr_flat_search_segments/compact");
-          if (last) finalized = true;
-        }
-      } else {
-      uint64_t begin = 0;
-      double endf = (double)n_sample_tiles * growth;  // in tiles
-      while (begin < total_tiles) {
-        uint64_t end = ((uint64_t)(endf + 0.5) + 7) & ~7ull;   // whole 256-row groups: the wide-row kernels' K order is a function of the global group (flat_scan_wide.hip)
-        if (end > total_tiles || (double)total_tiles < endf * 1.25) end = total_tiles;  // no sliver of a last chunk
-        if (end <= begin) end = begin + 8;
-        if (end > total_tiles) end = total_tiles;
-        a.tile_first = (uint32_t)begin; a.tile_stride = 1; a.n_tiles = (uint32_t)(end - begin);
-        a.timeline = rr::tuning_env("RR_SCAN_TIMELINE") ? (uint64_t*)w.dense : nullptr;  // the dense buffer is idle during chunk scans
-        RR_CHECK(profiled_scan(a, dtype, dim, false, grid, st), "rr_flat_search/scan");
-        const bool last = end == total_tiles;
-        RR_CHECK(launch_compact(s, (last && !half_sqnorm) ? &fin : nullptr, st), "rr_flat_search/compact");
-        if (last && !half_sqnorm) finalized = true;
-        begin = end;
-        endf *= growth;
-      }
-      }
-    }
-    if (!finalized)
-      RR_CHECK(launch_finalize(s, D_b, I_b, id_offset, segs ? nullptr : mask_b, mask_stride,
-                               half_sqnorm ? (const void*)xq_b : nullptr, dtype, dim, st),
-               "rr_flat_search/finalize");
-  }
-#undef RR_CHECK
-  return RR_OK;
+  return grid > 0 ? carve(nullptr, k, grid, RR_DTYPE_F16, dim).total : 0;
 }
 
 int rr_flat_search(const void* xb, int dtype, int64_t n_rows, int dim, const void* xq, int nq, int k, float* D,
                    int64_t* I, int64_t id_offset, void* ws, size_t ws_bytes, const uint8_t* route_mask,
                    int64_t mask_stride, void* stream) {
-  if (dtype != RR_DTYPE_F16 && dtype != RR_DTYPE_BF16) return fail(RR_ERR_INVALID, "rr_flat_search: bad dtype%s");
+  if (!rr::half_dtype(dtype)) return fail(RR_ERR_INVALID, "rr_flat_search: bad dtype%s");
   return flat_search_impl(xb, dtype, n_rows, dim, xq, nq, k, D, I, id_offset, ws, ws_bytes, route_mask, mask_stride, nullptr, stream);
 }
 
@@ -381,11 +397,10 @@ static int seg_host_from(const rr_segment* segs, int n_segs, int64_t n_rows_tota
 int rr_flat_search_segments(const void* xb, int dtype, int64_t n_rows_total, int dim, const rr_segment* segs, int n_segs,
                             const void* xq, int nq, int k, float* D, int64_t* I, void* ws, size_t ws_bytes,
                             const uint8_t* route_mask, int64_t mask_stride, void* stream) {
-  if (dtype != RR_DTYPE_F16 && dtype != RR_DTYPE_BF16) return fail(RR_ERR_INVALID, "rr_flat_search_segments: bad dtype%s");
+  if (!rr::half_dtype(dtype)) return fail(RR_ERR_INVALID, "rr_flat_search_segments: bad dtype%s");
   rr::SegHost h;
   int64_t scanned = 0;
-  const int rc = seg_host_from(segs, n_segs, n_rows_total, route_mask, mask_stride, "rr_flat_search_segments", h, scanned);
-  if (rc != RR_OK) return rc;
+  if (int rc = seg_host_from(segs, n_segs, n_rows_total, route_mask, mask_stride, "rr_flat_search_segments", h, scanned)) return rc;
   return flat_search_impl(xb, dtype, scanned, dim, xq, nq, k, D, I, 0, ws, ws_bytes, route_mask, mask_stride, nullptr, stream, &h);
 }
 
@@ -407,30 +422,27 @@ int rr_faithful_build(const float* xf32, int64_t ld_f32, const void* xb, int dty
                       void* stream) {
   if (n_rows < 0 || d < 1 || d > dim || ld_f32 < d || rr::scan_padded_dim(dim) != dim || !stats || ((!xf32 || !xb) && n_rows > 0))
     return fail(RR_ERR_INVALID, "rr_faithful_build: bad arguments%s");
-  if (dtype != RR_DTYPE_F16 && dtype != RR_DTYPE_BF16) return fail(RR_ERR_INVALID, "rr_faithful_build: bad dtype%s");
-  hipError_t e = rr::launch_faithful_build(xf32, ld_f32, xb, dtype, n_rows, d, dim, (uint32_t*)stats, (hipStream_t)stream);
-  return e == hipSuccess ? RR_OK : hip_fail(e, "rr_faithful_build");
+  if (!rr::half_dtype(dtype)) return fail(RR_ERR_INVALID, "rr_faithful_build: bad dtype%s");
+  return hip_status(rr::launch_faithful_build(xf32, ld_f32, xb, dtype, n_rows, d, dim, (uint32_t*)stats, (hipStream_t)stream), "rr_faithful_build");
 }
 
 struct FaithWs { float* eps; float* PL; int64_t* IL; char* inner; size_t inner_bytes, total; };
 static FaithWs carve_faithful(char* base, int list_len, int nq, int dim, int grid) {
   FaithWs w;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return base ? base + o : (char*)nullptr; };
-  w.eps = (float*)take((size_t)nq * sizeof(float));
-  w.PL = (float*)take((size_t)nq * list_len * sizeof(float));
-  w.IL = (int64_t*)take((size_t)nq * list_len * sizeof(int64_t));
-  w.inner_bytes = carve(nullptr, list_len, grid, dim).total;
-  w.inner = take(w.inner_bytes);
-  w.total = off;
+  Bump b{base};
+  w.eps = b.take<float>(nq);
+  w.PL = b.take<float>((size_t)nq * list_len);
+  w.IL = b.take<int64_t>((size_t)nq * list_len);
+  w.inner_bytes = carve(nullptr, list_len, grid, RR_DTYPE_F16, dim).total;
+  w.inner = b.take<char>(w.inner_bytes);
+  w.total = b.off;
   return w;
 }
 
 size_t rr_flat_search_faithful_workspace_bytes(int k, int list_len, int nq, int dim) {
   if (k < 1 || list_len < k || list_len > rr::kMaxK || nq < 0 || rr::scan_padded_dim(dim) != dim) return 0;
   const int grid = device_cus();
-  if (grid <= 0) return 0;
-  return carve_faithful(nullptr, list_len, nq, dim, grid).total;
+  return grid > 0 ? carve_faithful(nullptr, list_len, nq, dim, grid).total : 0;
 }
 
 int rr_flat_search_faithful(const void* xb, int dtype, const float* xf32, int64_t ld_f32, const float* stats, int64_t n_rows_total,
@@ -439,14 +451,13 @@ int rr_flat_search_faithful(const void* xb, int dtype, const float* xf32, int64_
                             const uint8_t* route_mask, int64_t mask_stride, void* stream) {
   using namespace rr;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype != RR_DTYPE_F16 && dtype != RR_DTYPE_BF16) return fail(RR_ERR_INVALID, "rr_flat_search_faithful: bad dtype%s");
+  if (!half_dtype(dtype)) return fail(RR_ERR_INVALID, "rr_flat_search_faithful: bad dtype%s");
   if (k < 1 || list_len < k || list_len > kMaxK) return fail(RR_ERR_INVALID, "rr_flat_search_faithful: need 1 <= k <= list_len <= 1024%s");
   if (scan_padded_dim(dim) != dim) return fail(RR_ERR_UNSUPPORTED, "rr_flat_search_faithful: dim must equal rr_padded_dim(d)%s");
   if (d < 1 || d > dim || ld_f32 < d || nq < 0) return fail(RR_ERR_INVALID, "rr_flat_search_faithful: bad sizes%s");
   SegHost h;
   int64_t scanned = 0;
-  int rc = seg_host_from(segs, n_segs, n_rows_total, route_mask, mask_stride, "rr_flat_search_faithful", h, scanned);
-  if (rc != RR_OK) return rc;
+  if (int rc = seg_host_from(segs, n_segs, n_rows_total, route_mask, mask_stride, "rr_flat_search_faithful", h, scanned)) return rc;
   if (nq == 0) return RR_OK;
   if (!xq || !xq_f32 || !D || !I || !exact || !ws || !stats || ((!xb || !xf32) && scanned > 0))
     return fail(RR_ERR_INVALID, "rr_flat_search_faithful: null pointer%s");
@@ -455,37 +466,34 @@ int rr_flat_search_faithful(const void* xb, int dtype, const float* xf32, int64_
   FaithWs w = carve_faithful((char*)ws, list_len, nq, dim, grid);
   if (ws_bytes < w.total) return fail(RR_ERR_WORKSPACE, "rr_flat_search_faithful: workspace smaller than rr_flat_search_faithful_workspace_bytes%s");
   float* e_out = eps ? eps : w.eps;
-  hipError_t e = launch_faithful_queries(xq_f32, xq, dtype, nq, d, dim, (const uint32_t*)stats, e_out, st);
-  if (e != hipSuccess) return hip_fail(e, "rr_flat_search_faithful/queries");
+  if (int rc = hip_status(launch_faithful_queries(xq_f32, xq, dtype, nq, d, dim, (const uint32_t*)stats, e_out, st),
+                          "rr_flat_search_faithful/queries")) return rc;
   // the half rows through the ordinary segmented scan at k' = list_len, listing MATRIX rows (id_offset := row_begin)
   const FaithSegs fs = faith_segs(h);
   for (uint32_t s = 0; s < h.n; ++s) h.id_offset[s] = h.row_begin[s];
-  rc = flat_search_impl(xb, dtype, scanned, dim, xq, nq, list_len, w.PL, w.IL, 0, w.inner, w.inner_bytes, route_mask, mask_stride,
-                        nullptr, stream, &h);
-  if (rc != RR_OK) return rc;
-  e = launch_faithful_rescore(xf32, ld_f32, d, xq_f32, nq, list_len, w.PL, w.IL, e_out, k, fs, route_mask, mask_stride, D, I, exact, st);
-  return e == hipSuccess ? RR_OK : hip_fail(e, "rr_flat_search_faithful/rescore");
+  if (int rc = flat_search_impl(xb, dtype, scanned, dim, xq, nq, list_len, w.PL, w.IL, 0, w.inner, w.inner_bytes, route_mask, mask_stride,
+                                nullptr, stream, &h)) return rc;
+  return hip_status(launch_faithful_rescore(xf32, ld_f32, d, xq_f32, nq, list_len, w.PL, w.IL, e_out, k, fs, route_mask, mask_stride, D, I, exact, st),
+                    "rr_flat_search_faithful/rescore");
 }
 
 // exact scan: per block of queries [G][k] lists -> (two-level if G*k > 8192) merge -> [k] -> D / I rows
 struct ExactWs { float *D1, *D2, *D3; int64_t *I1, *I2, *I3; size_t total; };
 static ExactWs carve_exact(char* base, const rr::FaithPlan& p, int k) {
   ExactWs w;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return base ? base + o : (char*)nullptr; };
+  Bump b{base};
   const size_t l1 = (size_t)p.nqb * p.G * k, l2 = (size_t)p.nqb * ((p.G + p.gs - 1) / p.gs) * k, l3 = (size_t)p.nqb * k;
-  w.D1 = (float*)take(l1 * 4); w.I1 = (int64_t*)take(l1 * 8);
-  w.D2 = (float*)take(l2 * 4); w.I2 = (int64_t*)take(l2 * 8);
-  w.D3 = (float*)take(l3 * 4); w.I3 = (int64_t*)take(l3 * 8);
-  w.total = off;
+  w.D1 = b.take<float>(l1); w.I1 = b.take<int64_t>(l1);
+  w.D2 = b.take<float>(l2); w.I2 = b.take<int64_t>(l2);
+  w.D3 = b.take<float>(l3); w.I3 = b.take<int64_t>(l3);
+  w.total = b.off;
   return w;
 }
 
 size_t rr_flat_search_f32_exact_workspace_bytes(int k, int d) {
   if (k < 1 || k > rr::kMaxK || d < 1 || d > rr::kMaxDim) return 0;
   const int grid = device_cus();
-  if (grid <= 0) return 0;
-  return carve_exact(nullptr, rr::faithful_plan(k, d, grid, -1), k).total;
+  return grid > 0 ? carve_exact(nullptr, rr::faithful_plan(k, d, grid, -1), k).total : 0;
 }
 
 int rr_flat_search_f32_exact(const float* xf32, int64_t ld_f32, int64_t n_rows_total, int d, const rr_segment* segs, int n_segs,
@@ -498,8 +506,7 @@ int rr_flat_search_f32_exact(const float* xf32, int64_t ld_f32, int64_t n_rows_t
     return fail(RR_ERR_INVALID, "rr_flat_search_f32_exact: bad sizes%s");
   SegHost h;
   int64_t scanned = 0;
-  int rc = seg_host_from(segs, n_segs, n_rows_total, route_mask, mask_stride, "rr_flat_search_f32_exact", h, scanned);
-  if (rc != RR_OK) return rc;
+  if (int rc = seg_host_from(segs, n_segs, n_rows_total, route_mask, mask_stride, "rr_flat_search_f32_exact", h, scanned)) return rc;
   if (n_idx == 0) return RR_OK;
   if (!xq_f32 || !D || !I || !ws || (!xf32 && scanned > 0)) return fail(RR_ERR_INVALID, "rr_flat_search_f32_exact: null pointer%s");
   const int grid = device_cus();
@@ -508,25 +515,22 @@ int rr_flat_search_f32_exact(const float* xf32, int64_t ld_f32, int64_t n_rows_t
   ExactWs w = carve_exact((char*)ws, p, k);
   if (ws_bytes < w.total) return fail(RR_ERR_WORKSPACE, "rr_flat_search_f32_exact: workspace smaller than rr_flat_search_f32_exact_workspace_bytes%s");
   const FaithSegs fs = faith_segs(h);
-  hipError_t e;
   for (int q0 = 0; q0 < n_idx; q0 += p.nqb) {
     const int nqb = n_idx - q0 < p.nqb ? n_idx - q0 : p.nqb;
-    e = launch_faithful_scan(p, xf32, ld_f32, d, scanned, xq_f32, qidx, q0, nqb, k, fs, route_mask, mask_stride, w.D1, w.I1, st);
-    if (e != hipSuccess) return hip_fail(e, "rr_flat_search_f32_exact/scan");
+    if (int rc = hip_status(launch_faithful_scan(p, xf32, ld_f32, d, scanned, xq_f32, qidx, q0, nqb, k, fs, route_mask, mask_stride, w.D1, w.I1, st),
+                            "rr_flat_search_f32_exact/scan")) return rc;
     const float* Dm = w.D1;
     const int64_t* Im = w.I1;
     int lists = p.G;
     if (lists > p.gs) {   // level 1: groups of gs consecutive lists of one query -> [nqb][G / gs][k]
       const MergeSrc src{w.D1, w.I1, p.gs * k, 1, 0, 0, 0};
-      e = launch_merge_topk(src, nqb * (lists / p.gs), p.gs * k, k, 1, w.D2, w.I2, st);
-      if (e != hipSuccess) return hip_fail(e, "rr_flat_search_f32_exact/merge1");
+      if (int rc = hip_status(launch_merge_topk(src, nqb * (lists / p.gs), p.gs * k, k, 1, w.D2, w.I2, st), "rr_flat_search_f32_exact/merge1"))
+        return rc;
       Dm = w.D2; Im = w.I2; lists /= p.gs;
     }
     const MergeSrc src{Dm, Im, lists * k, 1, 0, 0, 0};
-    e = launch_merge_topk(src, nqb, lists * k, k, 1, w.D3, w.I3, st);
-    if (e != hipSuccess) return hip_fail(e, "rr_flat_search_f32_exact/merge");
-    e = launch_faithful_emit(w.D3, w.I3, qidx, q0, nqb, k, fs, D, I, st);
-    if (e != hipSuccess) return hip_fail(e, "rr_flat_search_f32_exact/emit");
+    if (int rc = hip_status(launch_merge_topk(src, nqb, lists * k, k, 1, w.D3, w.I3, st), "rr_flat_search_f32_exact/merge")) return rc;
+    if (int rc = hip_status(launch_faithful_emit(w.D3, w.I3, qidx, q0, nqb, k, fs, D, I, st), "rr_flat_search_f32_exact/emit")) return rc;
   }
   return RR_OK;
 }
@@ -535,15 +539,14 @@ int rr_flat_search_f32_exact(const float* xf32, int64_t ld_f32, int64_t n_rows_t
 struct ScreenWs { int8_t* q8; float* qinfo; float* PL; int64_t* IL; char* inner; size_t inner_bytes, total; };
 static ScreenWs carve_screen(char* base, int list_len, int nq, int dim8, int grid) {
   ScreenWs w;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return base ? base + o : (char*)nullptr; };
-  w.q8 = (int8_t*)take((size_t)nq * dim8);
-  w.qinfo = (float*)take((size_t)nq * 2 * sizeof(float));
-  w.PL = (float*)take((size_t)nq * list_len * sizeof(float));
-  w.IL = (int64_t*)take((size_t)nq * list_len * sizeof(int64_t));
-  w.inner_bytes = carve(nullptr, list_len, grid, rr::kMaxResidentDim).total;
-  w.inner = take(w.inner_bytes);
-  w.total = off;
+  Bump b{base};
+  w.q8 = b.take<int8_t>((size_t)nq * dim8);
+  w.qinfo = b.take<float>((size_t)nq * 2);
+  w.PL = b.take<float>((size_t)nq * list_len);
+  w.IL = b.take<int64_t>((size_t)nq * list_len);
+  w.inner_bytes = carve(nullptr, list_len, grid, rr::kDtypeI8, dim8 / 2).total;
+  w.inner = b.take<char>(w.inner_bytes);
+  w.total = b.off;
   return w;
 }
 
@@ -557,17 +560,15 @@ int rr_screen_build(const void* xb, int dtype, int64_t n_rows, int dim, void* x8
   const int dim8 = rr_screen_dim(dim);
   if (dim8 < 0) return fail(dim8, "rr_screen_build: the int8 screening copy needs dim <= 1536, a multiple of 8%s");
   if (n_rows < 0 || !stats || ((!xb || !x8) && n_rows > 0)) return fail(RR_ERR_INVALID, "rr_screen_build: bad arguments%s");
-  if (dtype != RR_DTYPE_F16 && dtype != RR_DTYPE_BF16) return fail(RR_ERR_INVALID, "rr_screen_build: bad dtype%s");
-  hipError_t e = rr::launch_screen_build(xb, dtype, n_rows, dim, (int8_t*)x8, dim8, (uint32_t*)stats, (hipStream_t)stream);
-  return e == hipSuccess ? RR_OK : hip_fail(e, "rr_screen_build");
+  if (!rr::half_dtype(dtype)) return fail(RR_ERR_INVALID, "rr_screen_build: bad dtype%s");
+  return hip_status(rr::launch_screen_build(xb, dtype, n_rows, dim, (int8_t*)x8, dim8, (uint32_t*)stats, (hipStream_t)stream), "rr_screen_build");
 }
 
 size_t rr_flat_search_screened_workspace_bytes(int k, int list_len, int nq, int dim) {
   const int dim8 = rr_screen_dim(dim);
   if (k < 1 || list_len < k || list_len > rr::kMaxK || nq < 0 || dim8 < 0) return 0;
-  int grid = device_cus();
-  if (grid <= 0) return 0;
-  return carve_screen(nullptr, list_len, nq, dim8, grid).total;
+  const int grid = device_cus();
+  return grid > 0 ? carve_screen(nullptr, list_len, nq, dim8, grid).total : 0;
 }
 
 int rr_flat_search_screened(const void* xb, int dtype, const void* x8, const float* stats, int64_t n_rows, int dim, const void* xq,
@@ -578,7 +579,7 @@ int rr_flat_search_screened(const void* xb, int dtype, const void* x8, const flo
   const int dim8 = rr_screen_dim(dim);
   if (dim8 < 0) return fail(RR_ERR_UNSUPPORTED, "rr_flat_search_screened: dim must be a multiple of 8, <= 1536%s");
   if (k < 1 || list_len < k || list_len > kMaxK) return fail(RR_ERR_INVALID, "rr_flat_search_screened: need 1 <= k <= list_len <= 1024%s");
-  if (dtype != RR_DTYPE_F16 && dtype != RR_DTYPE_BF16) return fail(RR_ERR_INVALID, "rr_flat_search_screened: bad dtype%s");
+  if (!half_dtype(dtype)) return fail(RR_ERR_INVALID, "rr_flat_search_screened: bad dtype%s");
   if (nq < 0 || n_rows < 0) return fail(RR_ERR_INVALID, "rr_flat_search_screened: negative size%s");
   if (nq == 0) return RR_OK;
   if (!xq || !D || !I || !exact || !ws || !stats || ((!xb || !x8) && n_rows > 0))
@@ -587,20 +588,19 @@ int rr_flat_search_screened(const void* xb, int dtype, const void* x8, const flo
   if (grid <= 0) return fail(RR_ERR_HIP, "rr_flat_search_screened: no HIP device%s");
   ScreenWs w = carve_screen((char*)ws, list_len, nq, dim8, grid);
   if (ws_bytes < w.total) return fail(RR_ERR_WORKSPACE, "rr_flat_search_screened: workspace smaller than rr_flat_search_screened_workspace_bytes%s");
-  hipError_t e = launch_screen_queries(xq, dtype, nq, dim, w.q8, dim8, (const uint32_t*)stats, w.qinfo, st);
-  if (e != hipSuccess) return hip_fail(e, "rr_flat_search_screened/queries");
+  if (int rc = hip_status(launch_screen_queries(xq, dtype, nq, dim, w.q8, dim8, (const uint32_t*)stats, w.qinfo, st),
+                          "rr_flat_search_screened/queries")) return rc;
   // the int8 rows through the same scan + exact selection, k' = list_len; a row of dim8 bytes is dim8/2 two-byte elements
-  int rc = flat_search_impl(x8, kDtypeI8, n_rows, dim8 / 2, w.q8, nq, list_len, w.PL, w.IL, 0, w.inner, w.inner_bytes, nullptr, 0, nullptr, stream);
-  if (rc != RR_OK) return rc;
-  e = launch_rescore(xb, xq, dtype, dim, nq, list_len, w.PL, w.IL, w.qinfo, k, D, I, id_offset, exact, route_mask, mask_stride, st);
-  return e == hipSuccess ? RR_OK : hip_fail(e, "rr_flat_search_screened/rescore");
+  if (int rc = flat_search_impl(x8, kDtypeI8, n_rows, dim8 / 2, w.q8, nq, list_len, w.PL, w.IL, 0, w.inner, w.inner_bytes, nullptr, 0, nullptr,
+                                stream)) return rc;
+  return hip_status(launch_rescore(xb, xq, dtype, dim, nq, list_len, w.PL, w.IL, w.qinfo, k, D, I, id_offset, exact, route_mask, mask_stride, st),
+                    "rr_flat_search_screened/rescore");
 }
 
 int rr_half_sqnorms(const void* xb, int dtype, int64_t n_rows, int dim, float* out, void* stream) {
   if (n_rows < 0 || dim < 8 || dim % 8 != 0 || ((!xb || !out) && n_rows > 0)) return fail(RR_ERR_INVALID, "rr_half_sqnorms: bad arguments%s");
-  if (dtype != RR_DTYPE_F16 && dtype != RR_DTYPE_BF16) return fail(RR_ERR_INVALID, "rr_half_sqnorms: bad dtype%s");
-  hipError_t e = rr::launch_half_sqnorms(xb, dtype, n_rows, dim, out, (hipStream_t)stream);
-  return e == hipSuccess ? RR_OK : hip_fail(e, "rr_half_sqnorms");
+  if (!rr::half_dtype(dtype)) return fail(RR_ERR_INVALID, "rr_half_sqnorms: bad dtype%s");
+  return hip_status(rr::launch_half_sqnorms(xb, dtype, n_rows, dim, out, (hipStream_t)stream), "rr_half_sqnorms");
 }
 
 int rr_profile_begin(int max_launches) {
@@ -646,7 +646,7 @@ int rr_profile_end(double* scan_ms_total, int* n_launches, double* rows_scanned)
 
 const char* rr_flat_scan_kernel_name(int dim, int nq) {
   if (rr::scan_padded_dim(dim) != dim || nq < 1) return "";
-  return rr::scan_kernel_name(dim, nq > rr::kQueriesPerBlock ? rr::kQueriesPerBlock : nq, false);
+  return rr::scan_plan(RR_DTYPE_F16, dim, nq > rr::kQueriesPerBlock ? rr::kQueriesPerBlock : nq, false).name;
 }
 
 int rr_merge_topk(const float* Din, const int64_t* Iin, int nq, int m, int k, int descending, float* Dout,
@@ -656,8 +656,7 @@ int rr_merge_topk(const float* Din, const int64_t* Iin, int nq, int m, int k, in
   if (nq == 0) return RR_OK;
   if ((m > 0 && (!Din || !Iin)) || !Dout || !Iout) return fail(RR_ERR_INVALID, "rr_merge_topk: null pointer%s");
   const rr::MergeSrc src{Din, Iin, m > 0 ? m : 1, 1, 0, 0, 0};
-  hipError_t e = rr::launch_merge_topk(src, nq, m, k, descending, Dout, Iout, (hipStream_t)stream);
-  return e == hipSuccess ? RR_OK : hip_fail(e, "rr_merge_topk");
+  return hip_status(rr::launch_merge_topk(src, nq, m, k, descending, Dout, Iout, (hipStream_t)stream), "rr_merge_topk");
 }
 
 int rr_merge_topk_gathered(const void* gathered, int n_ranks, size_t rank_stride_bytes, size_t ids_offset_bytes, int slots, int nq,
@@ -674,40 +673,40 @@ int rr_merge_topk_gathered(const void* gathered, int n_ranks, size_t rank_stride
   if ((uintptr_t)gathered % 8 != 0) return fail(RR_ERR_INVALID, "rr_merge_topk_gathered: the buffer must be 8-byte aligned%s");
   const rr::MergeSrc src{(const float*)gathered, (const int64_t*)((const char*)gathered + ids_offset_bytes), k_in, slots,
                          (int64_t)(rank_stride_bytes / 4), (int64_t)(rank_stride_bytes / 8), (int64_t)list_elems};
-  hipError_t e = rr::launch_merge_topk(src, nq, (int)m, k, descending, Dout, Iout, (hipStream_t)stream);
-  return e == hipSuccess ? RR_OK : hip_fail(e, "rr_merge_topk_gathered");
+  return hip_status(rr::launch_merge_topk(src, nq, (int)m, k, descending, Dout, Iout, (hipStream_t)stream), "rr_merge_topk_gathered");
+}
+
+static bool router_header_ok(const rr_router_weights* w) {
+  return w && w->n_sources >= 1 && w->d_max >= 1 && w->n_models >= 1 && w->d_max <= 8448;
+}
+// Argument validation of the router entry points; `who` names the entry point in the messages.  nq == 0 needs no buffers.
+static int router_check(const rr_router_weights* w, const float* xq, int nq, float* logits, uint8_t* mask, const char* who) {
+  if (!w || nq < 0) return fail(RR_ERR_INVALID, "%s: bad arguments", who);
+  if (!router_header_ok(w)) return fail(RR_ERR_INVALID, "%s: bad weight header", who);
+  if (nq > 0 && (!xq || !logits || !mask || !w->w1q || !w->c1 || !w->w2 || !w->w3 || !w->model_of_source))
+    return fail(RR_ERR_INVALID, "%s: null pointer", who);
+  return RR_OK;
 }
 
 int rr_router_mlp(const rr_router_weights* w, const float* xq, int nq, float* logits, uint8_t* mask, void* stream) {
-  if (!w || nq < 0) return fail(RR_ERR_INVALID, "rr_router_mlp: bad arguments%s");
-  if (w->n_sources < 1 || w->d_max < 1 || w->n_models < 1 || w->d_max > 8448)
-    return fail(RR_ERR_INVALID, "rr_router_mlp: bad weight header%s");
+  if (int rc = router_check(w, xq, nq, logits, mask, "rr_router_mlp")) return rc;
   if (nq == 0) return RR_OK;
-  if (!xq || !logits || !mask || !w->w1q || !w->c1 || !w->w2 || !w->w3 || !w->model_of_source)
-    return fail(RR_ERR_INVALID, "rr_router_mlp: null pointer%s");
-  hipError_t e = rr::launch_router_mlp(w, xq, nq, logits, mask, (hipStream_t)stream);
-  return e == hipSuccess ? RR_OK : hip_fail(e, "rr_router_mlp");
+  return hip_status(rr::launch_router_mlp(w, xq, nq, logits, mask, (hipStream_t)stream), "rr_router_mlp");
 }
 
 size_t rr_router_workspace_bytes(const rr_router_weights* w, int nq) {
-  if (!w || nq < 0 || w->n_sources < 1 || w->d_max < 1 || w->n_models < 1 || w->d_max > 8448) return 0;
-  return rr::router_workspace_bytes(w, nq);
+  return nq >= 0 && router_header_ok(w) ? rr::router_workspace_bytes(w, nq) : 0;
 }
 
 int rr_router_mlp_ws(const rr_router_weights* w, const float* xq, int nq, float* logits, uint8_t* mask, void* ws, size_t ws_bytes,
                      void* stream) {
-  if (!w || nq < 0) return fail(RR_ERR_INVALID, "rr_router_mlp_ws: bad arguments%s");
-  if (w->n_sources < 1 || w->d_max < 1 || w->n_models < 1 || w->d_max > 8448)
-    return fail(RR_ERR_INVALID, "rr_router_mlp_ws: bad weight header%s");
+  if (int rc = router_check(w, xq, nq, logits, mask, "rr_router_mlp_ws")) return rc;
   if (nq == 0) return RR_OK;
-  if (!xq || !logits || !mask || !w->w1q || !w->c1 || !w->w2 || !w->w3 || !w->model_of_source)
-    return fail(RR_ERR_INVALID, "rr_router_mlp_ws: null pointer%s");
   const size_t need = rr::router_workspace_bytes(w, nq);
   if (need == 0)  // small batch: the latency-oriented kernel, no workspace
     return rr_router_mlp(w, xq, nq, logits, mask, stream);
   if (!ws || ws_bytes < need) return fail(RR_ERR_WORKSPACE, "rr_router_mlp_ws: workspace smaller than rr_router_workspace_bytes%s");
-  hipError_t e = rr::launch_router_mlp_ws(w, xq, nq, logits, mask, ws, (hipStream_t)stream);
-  return e == hipSuccess ? RR_OK : hip_fail(e, "rr_router_mlp_ws");
+  return hip_status(rr::launch_router_mlp_ws(w, xq, nq, logits, mask, ws, (hipStream_t)stream), "rr_router_mlp_ws");
 }
 
 }  // extern "C"

@@ -461,34 +461,6 @@ static hipError_t launch_scan_half_resident(const ScanArgs& a, int D, bool dense
   }
 }
 
-// 768 < D <= 1536: batches of at least this many queries take the wide-row kernel in one pass (RR_WIDE_MIN_QUERIES)
-static int wide_min_queries() {
-  static const int v = [] { const char* e = tuning_env("RR_WIDE_MIN_QUERIES"); return e ? atoi(e) : 129; }();
-  return v;
-}
-
-static bool half_resident_dim(int D) { return D == 896 || D == 1024 || D == 1280 || D == 1536; }
-// queries one scan launch serves: 256, or 128 where only 32 queries per wave stay resident (768 < D <= 1536) and the batch is small
-int scan_queries_per_launch(int D, int nq) {
-  return (half_resident_dim(D) && nq < wide_min_queries()) ? 128 : 256;  // (an L2 search at these dims still works in 128-query blocks: each goes to the wide-row kernel)
-}
-
-// 16-query blocks each wave keeps resident in the kernel that will serve (D, nq, metric): 4 (d <= 768), 2 (768 < d <= 1536 and a
-// small inner-product batch), 4 = the wide-row kernels (they stream the queries, from the same layout).  The prep kernel lays the
-// queries out accordingly (fragment order).
-int scan_query_blocks_per_wave(int D, int nq, bool l2) {
-  if (D <= kMaxResidentDim) return 4;
-  if (half_resident_dim(D) && nq < wide_min_queries() && !l2) return 2;
-  return 4;   // wide-row kernels: the 16 blocks of a 256-query pass, same [block][k slice][lane][8] order
-}
-
-// candidate buffers per (workgroup, query) of the kernel that will serve this block: 4 lane quarters; the row-split wide-row
-// kernel 8 (two waves share each query)
-int scan_bufs_per_wg(int D, int nq, bool l2, int k) {
-  if (half_resident_dim(D) && nq < wide_min_queries() && !l2) return 4;
-  return scan_wide_rowsplit(D, nq, l2, k) ? 8 : 4;
-}
-
 template <typename T, int D, bool DENSE, bool NT = false, bool L2 = false, bool SEG = false>
 static hipError_t launch_scan16(const ScanArgs& a, int grid, hipStream_t st) {
   const size_t lds = scan16_slots(D) * ((size_t)kTileRows * D * 2 + 256);  // ring + L2 norm slots
@@ -537,22 +509,41 @@ static hipError_t launch_scan_i8(const ScanArgs& a, int D, bool dense, int grid,
 #undef RR_I8_CASE
 }
 
-hipError_t launch_flat_scan(const ScanArgs& a, int dtype, int D, bool dense, int grid, hipStream_t st) {
-  if (dtype == kDtypeI8) return a.half_sqnorm ? hipErrorNotSupported : launch_scan_i8(a, D, dense, grid, st);
-  if (dtype != RR_DTYPE_F16 && dtype != RR_DTYPE_BF16) return hipErrorInvalidValue;
-  const bool f16 = dtype == RR_DTYPE_F16;
-  if (half_resident_dim(D) && (int)a.nq < wide_min_queries() && !a.half_sqnorm)  // 768 < D <= 1536, small batch: 32 resident queries per wave
-    return f16 ? launch_scan_half_resident<_Float16>(a, D, dense, grid, st) : launch_scan_half_resident<__bf16>(a, D, dense, grid, st);
-  if (D > kMaxResidentDim)  // wide rows (flat_scan_wide.hip); at 768 < D <= 1536 one pass of it beats two passes of the half-resident kernel
-    return launch_scan_wide(a, dtype, D, dense, grid, st);
-  return f16 ? launch_scan_d<_Float16>(a, D, dense, grid, st) : launch_scan_d<__bf16>(a, D, dense, grid, st);
+// 768 < D <= 1536: batches of at least this many queries take the wide-row kernel in one pass (RR_WIDE_MIN_QUERIES); at these
+// widths one pass of it beats two passes of the half-resident kernel
+static int wide_min_queries() {
+  static const int v = [] { const char* e = tuning_env("RR_WIDE_MIN_QUERIES"); return e ? atoi(e) : 129; }();
+  return v;
 }
+static bool half_resident_dim(int D) { return D == 896 || D == 1024 || D == 1280 || D == 1536; }
+// a small inner-product batch at 768 < D <= 1536: flat_scan16h_kernel, 32 resident queries per wave
+static bool half_resident_serves(int D, int nq, bool l2) { return half_resident_dim(D) && nq < wide_min_queries() && !l2; }
 
-// the kernel launch_flat_scan dispatches a filter launch of (D, nq queries in the block) to
-const char* scan_kernel_name(int D, int nq, bool l2) {
-  if (half_resident_dim(D) && nq < wide_min_queries() && !l2) return "flat_scan16h_kernel";
-  if (D > kMaxResidentDim) return scan_wide_kernel_name(D, nq);
-  return "flat_scan16_kernel";
+// queries one scan launch serves: 256, or 128 where only 32 queries per wave stay resident and the batch is small (an L2 search at
+// these dims works in 128-query blocks too: each goes to the wide-row kernel)
+int scan_queries_per_launch(int D, int nq) { return half_resident_serves(D, nq, false) ? 128 : 256; }
+
+ScanPlan scan_plan(int dtype, int D, int nq, bool l2) {
+  if (dtype == kDtypeI8) return {ScanKernel::kScan16I8, "flat_scan16_kernel", dtype, D, 4, 4, 0};   // int8 screening scan: D = bytes per row / 2
+  if (half_resident_serves(D, nq, l2)) return {ScanKernel::kScan16h, "flat_scan16h_kernel", dtype, D, 4, 2, 0};
+  if (D > kMaxResidentDim) return scan_plan_wide(dtype, D, nq);   // they stream the queries, from the 4-blocks-per-wave layout
+  return {ScanKernel::kScan16, "flat_scan16_kernel", dtype, D, 4, 4, 0};
+}
+// bufs_per_wg only grows with nq (the row-split kernel takes the largest blocks) and the half-resident kernel has 4: a full block, L2
+int scan_max_bufs_per_wg(int dtype, int D) { return scan_plan(dtype, D, kQueriesPerBlock, true).bufs_per_wg; }
+
+hipError_t launch_flat_scan(const ScanArgs& a, const ScanPlan& p, bool dense, int grid, hipStream_t st) {
+  if (p.kernel == ScanKernel::kScan16I8) return a.half_sqnorm ? hipErrorNotSupported : launch_scan_i8(a, p.D, dense, grid, st);
+  if (!half_dtype(p.dtype)) return hipErrorInvalidValue;
+  const bool f16 = p.dtype == RR_DTYPE_F16;
+  switch (p.kernel) {
+    case ScanKernel::kScan16h:
+      return f16 ? launch_scan_half_resident<_Float16>(a, p.D, dense, grid, st) : launch_scan_half_resident<__bf16>(a, p.D, dense, grid, st);
+    case ScanKernel::kScan16:
+      return f16 ? launch_scan_d<_Float16>(a, p.D, dense, grid, st) : launch_scan_d<__bf16>(a, p.D, dense, grid, st);
+    default:
+      return launch_scan_wide(a, p, dense, grid, st);   // flat_scan_wide.hip
+  }
 }
 
 int scan_padded_dim(int d) {

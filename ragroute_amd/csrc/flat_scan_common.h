@@ -325,8 +325,7 @@ hipError_t launch_with_lds(K kernel, int grid, int block, size_t lds, hipStream_
 }
 
 // flat_scan_wide.hip
-hipError_t launch_scan_wide(const ScanArgs& a, int dtype, int D, bool dense, int grid, hipStream_t st);
-const char* scan_wide_kernel_name(int D, int nq);
-bool scan_wide_rowsplit(int D, int nq, bool l2, int k);   // the row-split kernel serves this launch (8 candidate buffers per workgroup and query)
+ScanPlan scan_plan_wide(int dtype, int D, int nq);   // scan_plan's answer for wide rows
+hipError_t launch_scan_wide(const ScanArgs& a, const ScanPlan& p, bool dense, int grid, hipStream_t st);
 
 }  // namespace rr

@@ -803,23 +803,15 @@ __global__ __launch_bounds__(512) void flat_scan_wide_rs_kernel(const ScanArgs a
 
 // Filter launches: two waves per SIMD (flat_scan_wide8_kernel) up to d = 2048, one above.  Measured, 2M rows x 256 queries, whole
 // search: d = 1024 3.53 vs 3.43 TB/s, 1536 3.61 vs 3.50, 2048 3.74 vs 3.64, 4096 3.74 vs 3.82.  RR_WIDE_WAVES=4|8 forces one.
-static int wide_waves(int D) {
-  static const int forced = [] {
-    const char* e = tuning_env("RR_WIDE_WAVES");
-    const int v = e ? atoi(e) : 0;
-    return (v == 4 || v == 8) ? v : 0;
-  }();
-  return forced ? forced : (D <= 2048 ? 8 : 4);
-}
 // 129 ... 192 queries at d <= 2048: the 8-wave kernel deals 2 blocks per wave, so two SIMDs carry two busy waves and two carry one;
 // the 4-wave kernel's 3-block instance is level.  Measured (2M x 2048 / 4M x 1024, scan fraction): 129 queries 0.61 -> 0.66,
 // 160 queries 0.605 (8 waves) against 0.59, 192 queries 0.575 -> 0.60, 224 and 256 queries 8 waves (0.54 / 0.51 against 0.505 / 0.50).
 static int wide_waves_for(int D, int nq) {
-  const int w = wide_waves(D);
-  static const bool forced = tuning_env("RR_WIDE_WAVES") != nullptr;
-  if (forced || w != 8) return w;
+  static const char* const env = tuning_env("RR_WIDE_WAVES");
+  static const int forced = env ? atoi(env) : 0;
+  if (forced == 4 || forced == 8) return forced;
   const int nblk = (nq + 15) / 16;
-  return (nblk == 9 || nblk == 11 || nblk == 12) ? 4 : 8;
+  return (D > 2048 || (!env && (nblk == 9 || nblk == 11 || nblk == 12))) ? 4 : 8;
 }
 
 // 209 ... 256 queries at d > 768, 193 ... 256 at d > 2048 (round 4: either metric, any k; a workgroup owns 8 candidate buffers per query there): the row-split
@@ -827,7 +819,7 @@ static int wide_waves_for(int D, int nq) {
 // Measured against the kernels it replaces (scan launches, 256 queries): d = 1024 0.522-0.529 vs 0.510-0.515, 2048 0.527-0.530 vs
 // 0.512-0.521, 3072 0.521-0.524 vs 0.510-0.512, 4096 0.525-0.526 vs 0.511-0.513, 8192 0.516-0.517 vs 0.501-0.505; with 208 queries
 // or fewer the kernels that leave query quarters out win (160 queries: 0.61 against 0.52).
-bool scan_wide_rowsplit(int D, int nq, bool l2, int k) {
+static bool wide_rowsplit(int D, int nq) {
   static const bool on = [] { const char* e = tuning_env("RR_WIDE_RS"); return !(e && atoi(e) == 0) && !tuning_env("RR_WIDE_WAVES"); }();
   static const int max_d = [] { const char* e = tuning_env("RR_WIDE_RS_MAXD"); return e ? atoi(e) : kMaxDim; }();   // (tuning runs)
   // fewest queries it takes: 209 at d <= 2048 (13 blocks run as well or better on the 8-wave kernel: 200 queries 0.524 / 0.531 against
@@ -835,32 +827,34 @@ bool scan_wide_rowsplit(int D, int nq, bool l2, int k) {
   // the 4-wave kernel (193 / 200 / 208 queries at d = 4096: 0.530-0.534 against 0.509-0.512; profiles/r04/rowsplit_widening.json)
   static const int min_q_env = [] { const char* e = tuning_env("RR_WIDE_RS_MINQ"); return e ? atoi(e) : 0; }();
   const int min_q = min_q_env ? min_q_env : (D > 2048 ? 193 : 209);
-  return on && D > kMaxResidentDim && D <= max_d && nq >= min_q && k <= kMaxK;
+  return on && D > kMaxResidentDim && D <= max_d && nq >= min_q;
 }
-// name of the filter-launch kernel launch_scan_wide_t picks (reported by rr_flat_scan_kernel_name)
-const char* scan_wide_kernel_name(int D, int nq) {
-  if (scan_wide_rowsplit(D, nq, false, 32)) return "flat_scan_wide_rs_kernel";
-  return wide_waves_for(D, nq) == 8 ? "flat_scan_wide8_kernel" : "flat_scan_wide_pd_kernel";
+
+// The wide-row part of the scan plan (filter launches; dense launches always take the 4-wave kernel).  Query blocks (16 queries)
+// per wave: the batch is dealt evenly to the waves, so 17 ... 128 queries do not sit on one or two SIMDs.  Four-wave kernel:
+// consecutive blocks per wave (wide_nqb).  Eight-wave kernel: 1 block per wave up to 64 queries (measured at d = 2048, 128 queries:
+// 2 blocks on four waves 0.76, 1 block on eight 0.73 - every LDS fragment read then feeds one MFMA instead of two).
+ScanPlan scan_plan_wide(int dtype, int D, int nq) {
+  const int nqb4 = nq <= 64 ? 1 : nq <= 128 ? 2 : nq <= 192 ? 3 : 4;
+  if (wide_rowsplit(D, nq)) return {ScanKernel::kWideRs, "flat_scan_wide_rs_kernel", dtype, D, 8, 4, nqb4};   // two waves share each query: 8 buffers
+  if (wide_waves_for(D, nq) == 8) return {ScanKernel::kWide8, "flat_scan_wide8_kernel", dtype, D, 4, 4, nqb4};
+  return {ScanKernel::kWidePd, "flat_scan_wide_pd_kernel", dtype, D, 4, 4, nqb4};
 }
 
 template <typename T>
-static hipError_t launch_scan_wide_t(const ScanArgs& a, int D, bool dense, int grid, hipStream_t st) {
+static hipError_t launch_scan_wide_t(const ScanArgs& a, const ScanPlan& p, bool dense, int grid, hipStream_t st) {
+  const int D = p.D, nqb4 = p.wide_nqb;
   if (D % 128 != 0) return hipErrorInvalidValue;
   const size_t lds = (size_t)4 * (dense ? 1 : 8) * 4096;   // prefetch distance 2: a ring of 4 slots
-  const bool l2 = a.half_sqnorm != nullptr;
-  // query blocks (16 queries) per wave: the batch is dealt evenly to the waves, so 17 ... 128 queries no longer sit on one or two SIMDs
-  const int nqb4 = a.nq <= 64 ? 1 : a.nq <= 128 ? 2 : a.nq <= 192 ? 3 : 4;   // four-wave kernel (consecutive blocks per wave)
-  const bool one8 = a.nq <= 64;                            // eight-wave kernel: 1 block per wave up to 64 queries (measured at d = 2048,
-                                                           // 128 queries: 2 blocks on four waves 0.76, 1 block on eight 0.73 - every LDS
-                                                           // fragment read then feeds one MFMA instead of two)
+  const bool l2 = a.half_sqnorm != nullptr, one8 = nqb4 == 1;
 #define RR_LAUNCH_PD(DENSE_, L2_, NQB_) return launch_with_lds(flat_scan_wide_pd_kernel<T, DENSE_, L2_, NQB_>, grid, 256, lds, st, a, D);
-  if (!dense && scan_wide_rowsplit(D, (int)a.nq, l2, a.k)) {
+  if (!dense && p.kernel == ScanKernel::kWideRs) {
     const size_t lds_rs = (size_t)5 * 8 * 4096;   // 3 corpus + 2 query slots of 32 KB: all 160 KB
     if (l2 && a.ranges) return hipErrorNotSupported;
     if (l2) return launch_with_lds(flat_scan_wide_rs_kernel<T, true>, grid, 512, lds_rs, st, a, D);
     return launch_with_lds(flat_scan_wide_rs_kernel<T, false>, grid, 512, lds_rs, st, a, D);
   }
-  if (!dense && wide_waves_for(D, (int)a.nq) == 8) {
+  if (!dense && p.kernel == ScanKernel::kWide8) {
 #define RR_LAUNCH_8(L2_, NQB_) return launch_with_lds(flat_scan_wide8_kernel<T, L2_, NQB_>, grid, 512, lds, st, a, D);
     if (l2) { if (one8) RR_LAUNCH_8(true, 1) else RR_LAUNCH_8(true, 2) }
     if (one8) RR_LAUNCH_8(false, 1) else RR_LAUNCH_8(false, 2)
@@ -883,8 +877,8 @@ static hipError_t launch_scan_wide_t(const ScanArgs& a, int D, bool dense, int g
 #undef RR_LAUNCH_PD
 }
 
-hipError_t launch_scan_wide(const ScanArgs& a, int dtype, int D, bool dense, int grid, hipStream_t st) {
-  return dtype == RR_DTYPE_F16 ? launch_scan_wide_t<_Float16>(a, D, dense, grid, st) : launch_scan_wide_t<__bf16>(a, D, dense, grid, st);
+hipError_t launch_scan_wide(const ScanArgs& a, const ScanPlan& p, bool dense, int grid, hipStream_t st) {
+  return p.dtype == RR_DTYPE_F16 ? launch_scan_wide_t<_Float16>(a, p, dense, grid, st) : launch_scan_wide_t<__bf16>(a, p, dense, grid, st);
 }
 
 }  // namespace rr

@@ -46,13 +46,25 @@ struct ScanArgs {
   int cap, k;
 };
 
+inline bool half_dtype(int dtype) { return dtype == RR_DTYPE_F16 || dtype == RR_DTYPE_BF16; }
+
 // flat_scan.hip
-hipError_t launch_flat_scan(const ScanArgs& a, int dtype, int D, bool dense, int grid, hipStream_t st);
+// The scan plan: which kernel serves the filter launches of one block of nq queries, and the two layouts that follow from that
+// choice.  scan_plan() is the only place the choice is made; prep, scan, compaction and finalize of the block all read this object.
+enum class ScanKernel { kScan16, kScan16I8, kScan16h, kWidePd, kWide8, kWideRs };
+struct ScanPlan {
+  ScanKernel kernel;
+  const char* name;      // as rr_flat_scan_kernel_name reports it
+  int dtype, D;
+  int bufs_per_wg;       // candidate buffers per (workgroup, query): the stride of cand / cand_cnt is grid x this (4, row-split 8)
+  int blocks_per_wave;   // 16-query blocks per wave in the fragment-order copy prep_kernel writes into xqs (4, half-resident 2)
+  int wide_nqb;          // wide rows: 16-query blocks per wave of the 4-wave kernel (1 .. 4); the 8-wave kernel runs 1 where this is 1, else 2
+};
+ScanPlan scan_plan(int dtype, int D, int nq, bool l2);   // nq = queries of the block
+int scan_max_bufs_per_wg(int dtype, int D);              // the largest bufs_per_wg of any block at this width: sizes the workspace
+int scan_queries_per_launch(int D, int nq);              // nq = queries of the whole call
+hipError_t launch_flat_scan(const ScanArgs& a, const ScanPlan& p, bool dense, int grid, hipStream_t st);
 int scan_padded_dim(int d);
-const char* scan_kernel_name(int D, int nq, bool l2);  // filter-launch kernel for a block of nq queries
-int scan_bufs_per_wg(int D, int nq, bool l2, int k);   // candidate buffers per (workgroup, query) of the kernel that will serve the block
-int scan_queries_per_launch(int D, int nq);  // nq = queries of the whole call
-int scan_query_blocks_per_wave(int D, int nq, bool l2);  // 4 / 2: 16-query blocks per wave in the fragment-order copy the kernel reads
 
 // select.hip
 struct SelectArgs {

@@ -133,3 +133,40 @@ def test_isa_check_flags_a_prefetch_register_reused_before_the_drain():
     assert len(_build.check_prefetch_registers("\n".join(in_loop))) == 1
     other = "\n".join(bad).replace("flat_scan_wide_pd_kernel", "flat_scan16_kernel__")
     assert _build.check_prefetch_registers(other) == []
+
+
+# rr_flat_scan_kernel_name(dim, nq) for nq = 1 ... 256 and 300, run-length encoded per group of widths.  Recorded from the library
+# before kernel choice moved into rr::scan_plan, so it pins what the plan must keep answering.
+_S16, _S16H, _PD, _W8, _RS = ("flat_scan16_kernel", "flat_scan16h_kernel", "flat_scan_wide_pd_kernel", "flat_scan_wide8_kernel",
+                              "flat_scan_wide_rs_kernel")
+_WIDE_TO_2048 = [(16, _PD), (16, _W8), (32, _PD), (16, _W8), (49, _RS)]     # 129 ...: 9, 11 and 12 query blocks on four waves; row-split from 209
+SCAN_KERNEL_TABLE = [
+    ((128, 256, 384, 512, 640, 768), [(257, _S16)]),
+    ((896, 1024, 1280, 1536), [(128, _S16H)] + _WIDE_TO_2048),
+    ((1664, 1792, 1920, 2048), [(128, _W8)] + _WIDE_TO_2048),
+    (tuple(range(2176, 8193, 128)), [(192, _PD), (65, _RS)]),
+]
+
+
+def test_scan_plan_names_every_width_and_batch():
+    from ragroute_amd import _lib
+    L = _lib.lib()
+    nqs = list(range(1, 257)) + [300]
+    table = {d: [name for count, name in rle for _ in range(count)] for dims, rle in SCAN_KERNEL_TABLE for d in dims}
+    assert sorted(table) == sorted({L.rr_padded_dim(d) for d in range(1, 8193)}), "the table covers every value rr_padded_dim returns"
+    for d, want in table.items():
+        assert len(want) == len(nqs)
+        got = [L.rr_flat_scan_kernel_name(d, q).decode() for q in nqs]
+        wrong = [(q, g, w) for q, g, w in zip(nqs, got, want) if g != w]
+        assert not wrong, "dim %d: (nq, got, expected) %s" % (d, wrong[:5])
+    assert L.rr_flat_scan_kernel_name(1000, 5) == b"" and L.rr_flat_scan_kernel_name(768, 0) == b""
+
+
+def test_kernel_choice_is_written_once():
+    """The half-resident predicate appears once in csrc/, and the five functions that each re-derived the choice are gone."""
+    csrc = os.path.join(ROOT, "ragroute_amd", "csrc")
+    src = "".join(open(os.path.join(csrc, f)).read() for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    assert len(re.findall(r"half_resident_dim\(D\)\s*&&\s*\(?(?:int\))?\s*(?:a\.)?nq\s*<\s*wide_min_queries\(\)", src)) == 1
+    assert len(re.findall(r"\bwide_min_queries\(\)", src)) == 2, "its definition and the one predicate"
+    retired = re.findall(r"\b(?:scan_kernel_name|scan_bufs_per_wg|scan_query_blocks_per_wave|scan_wide_kernel_name|scan_wide_rowsplit)\b", src)
+    assert not retired, "kernel choice lives in rr::scan_plan (DESIGN.md): %s" % sorted(set(retired))
