@@ -109,7 +109,8 @@ int rr_flat_search(const void* d_xb, int dtype, int64_t n_rows, int dim, const v
  *             row), i.e. by ascending id when the id_offsets ascend with the segments.
  *   d_route_mask  optional device u8 [nq][mask_stride]: segment s serves query q iff mask_col < 0 or
  *             d_route_mask[q * mask_stride + mask_col] != 0 (router.py:276-282); a query routed nowhere gets all padding.
- *   d_ws      as rr_flat_search (rr_flat_search_workspace_bytes(k)).  Inner product / cosine only. */
+ *   d_ws      as rr_flat_search (rr_flat_search_workspace_bytes(k)).
+ * Inner product / cosine; the same search under the squared-L2 metric is rr_flat_search_segments_l2 below. */
 typedef struct rr_segment {
   int64_t row_begin;
   int64_t n_rows;
@@ -131,6 +132,23 @@ int rr_flat_search_l2(const void* d_xb, const float* d_half_sqnorm, int dtype, i
                       const uint8_t* d_route_mask, int64_t mask_stride, void* stream);
 /* |x|^2 / 2 (f32) of every row of a stored corpus, computed from the stored (rounded) values. */
 int rr_half_sqnorms(const void* d_xb, int dtype, int64_t n_rows, int dim, float* d_out, void* stream);
+
+/* rr_flat_search_segments under the squared-L2 metric: ONE search over the sources of one encoder whose index files are L2.  The
+ * reference's wikipedia federation has this shape - ten sources behind facebook/dpr-question_encoder-single-nq-base (config.py:35,
+ * 59-70), each asked with `index.search` (data_source.py:203), the replies concatenated (http_server.py:280-293) and the k LOWEST
+ * scores kept (`rerank_wikipedia`, rerank.py:28-34).  Per query: the k nearest rows of the union of the segments the router selected
+ * for it, nearest first, d_D = |q - x|^2 - what the ascending merge of the per-source rr_flat_search_l2 results yields, with one
+ * query preparation, one bootstrap and one chunk schedule for all sources.
+ *   d_half_sqnorm  device f32 [n_rows_total], aligned with d_xb: |x|^2 / 2 of every row (rr_half_sqnorms on each segment's rows, or
+ *             on the whole matrix); entries of alignment-gap rows are unspecified like the rows themselves (NaN, inf, anything):
+ *             scanned, never returned.  May be NULL only when the segments hold no rows.
+ *   d_I       ids as rr_flat_search_segments; ties by (segment order, row), i.e. ascending id when the id_offsets ascend.
+ *   padding   (+inf, -1): a query routed to no segment, or a federation with fewer than k rows.
+ *   d_ws      rr_flat_search_workspace_bytes_for(k, dim) bytes (or rr_flat_search_workspace_bytes(k)).
+ * Arguments are validated as by rr_flat_search_segments (same statuses and messages); nq == 0 is a no-op. */
+int rr_flat_search_segments_l2(const void* d_xb, const float* d_half_sqnorm, int dtype, int64_t n_rows_total, int dim,
+                               const rr_segment* segs, int n_segs, const void* d_xq, int nq, int k, float* d_D, int64_t* d_I,
+                               void* d_ws, size_t ws_bytes, const uint8_t* d_route_mask, int64_t mask_stride, void* stream);
 
 /* ---- Optional: the same exact inner-product top-k through an int8 screening copy --------------------------------------
  * Same call site as rr_flat_search (`index.search`, ragroute/data_source.py:158,186,203) and the same results; the

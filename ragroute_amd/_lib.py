@@ -19,7 +19,7 @@ EXPORTS = ("rr_version", "rr_last_error", "rr_device_cus", "rr_padded_dim", "rr_
            "rr_flat_search_screened_workspace_bytes", "rr_flat_search_screened", "rr_router_workspace_bytes", "rr_router_mlp_ws",
            "rr_build_flags", "rr_merge_topk_gathered", "rr_flat_scan_kernel_name", "rr_flat_search_segments", "rr_flat_search_workspace_bytes_for",
            "rr_faithful_build", "rr_flat_search_faithful_workspace_bytes", "rr_flat_search_faithful",
-           "rr_flat_search_f32_exact_workspace_bytes", "rr_flat_search_f32_exact")
+           "rr_flat_search_f32_exact_workspace_bytes", "rr_flat_search_f32_exact", "rr_flat_search_segments_l2")
 
 
 class RouterWeightsStruct(ctypes.Structure):
@@ -69,6 +69,8 @@ def lib():
         L.rr_flat_search.argtypes = [vp, i32, i64, i32, vp, i32, i32, vp, vp, i64, vp, sz, vp, i64, vp]
         L.rr_merge_topk.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
         L.rr_flat_search_segments.argtypes = [vp, i32, i64, i32, ctypes.POINTER(SegmentStruct), i32, vp, i32, i32, vp, vp, vp, sz, vp, i64, vp]
+        L.rr_flat_search_segments_l2.argtypes = [vp, vp, i32, i64, i32, ctypes.POINTER(SegmentStruct), i32, vp, i32, i32, vp, vp, vp, sz, vp,
+                                                 i64, vp]
         L.rr_merge_topk_gathered.argtypes = [vp, i32, sz, sz, i32, i32, i32, i32, i32, vp, vp, vp]
         L.rr_build_flags.restype = ctypes.c_char_p
         L.rr_flat_scan_kernel_name.argtypes = [i32, i32]

@@ -219,18 +219,27 @@ int schedule_segment_chunks(Block& b, const Schedule& sc, const rr::RangeEntry* 
   return RR_OK;
 }
 
-// segs != nullptr: segmented search — xb is ONE matrix of n_rows rows holding several sources (segs->row_begin / row_limit),
-// scanned as one corpus; route_mask then is [nq][mask_stride] with one column per segment (segs->mask_col), id_offset unused.
-int flat_search_impl(const void* xb, int dtype, int64_t n_rows, int dim, const void* xq, int nq, int k, float* D, int64_t* I,
-                     int64_t id_offset, void* ws, size_t ws_bytes, const uint8_t* route_mask, int64_t mask_stride,
-                     const float* half_sqnorm, void* stream, rr::SegHost* segs = nullptr) {
+// What a search checks before it looks at a pointer (every entry point of the flat search reports these the same way).
+int check_search_sizes(int dtype, int64_t n_rows, int dim, int nq, int k) {
   using namespace rr;
-  hipStream_t st = (hipStream_t)stream;
   if (k < 1 || k > kMaxK) return fail(RR_ERR_INVALID, "rr_flat_search: k must be in [1, 1024]%s");
   if (nq < 0 || n_rows < 0) return fail(RR_ERR_INVALID, "rr_flat_search: negative size%s");
   if (n_rows > 0xFFFFFFE0ll) return fail(RR_ERR_UNSUPPORTED, "rr_flat_search: more than 2^32-32 rows per shard%s");
   if (!half_dtype(dtype) && dtype != kDtypeI8) return fail(RR_ERR_INVALID, "rr_flat_search: bad dtype%s");
   if (scan_padded_dim(dim) != dim) return fail(RR_ERR_UNSUPPORTED, "rr_flat_search: dim must equal rr_padded_dim(d)%s");
+  return RR_OK;
+}
+
+// segs != nullptr: segmented search — xb is ONE matrix of n_rows rows holding several sources (segs->row_begin / row_limit),
+// scanned as one corpus; route_mask then is [nq][mask_stride] with one column per segment (segs->mask_col), id_offset unused.
+// half_sqnorm != nullptr: the squared-L2 metric (|x|^2 / 2 per matrix row), plain or segmented: same schedules, the scan ranks by
+// q.x - |x|^2/2 and launch_finalize turns the list into distances.
+int flat_search_impl(const void* xb, int dtype, int64_t n_rows, int dim, const void* xq, int nq, int k, float* D, int64_t* I,
+                     int64_t id_offset, void* ws, size_t ws_bytes, const uint8_t* route_mask, int64_t mask_stride,
+                     const float* half_sqnorm, void* stream, rr::SegHost* segs = nullptr) {
+  using namespace rr;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = check_search_sizes(dtype, n_rows, dim, nq, k)) return rc;
   if (nq == 0) return RR_OK;
   if (!xq || !D || !I || !ws || (!xb && n_rows > 0)) return fail(RR_ERR_INVALID, "rr_flat_search: null pointer%s");
   const int grid = device_cus();
@@ -301,7 +310,7 @@ const char kBuildFlags[] = "unknown (not built by ragroute_amd/_build.py)";
 
 extern "C" {
 
-int rr_version(void) { return 600; }  // 0.6.0: f32-faithful exact search (rr_flat_search_faithful, rr_flat_search_f32_exact); 0.5.0: row-split wide-row kernel for L2 / any k / 193+ queries (8 candidate buffers per workgroup on wide rows at every k: larger workspace), tuning variables ignored by product builds, cursor-free plain scans
+int rr_version(void) { return 700; }  // 0.7.0: segmented squared-L2 search (rr_flat_search_segments_l2); 0.6.0: f32-faithful exact search (rr_flat_search_faithful, rr_flat_search_f32_exact); 0.5.0: row-split wide-row kernel for L2 / any k / 193+ queries (8 candidate buffers per workgroup on wide rows at every k: larger workspace), tuning variables ignored by product builds, cursor-free plain scans
 const char* rr_build_flags(void) { return kBuildFlags; }
 const char* rr_last_error(void) { return g_err; }
 int rr_device_cus(void) {
@@ -402,6 +411,22 @@ int rr_flat_search_segments(const void* xb, int dtype, int64_t n_rows_total, int
   int64_t scanned = 0;
   if (int rc = seg_host_from(segs, n_segs, n_rows_total, route_mask, mask_stride, "rr_flat_search_segments", h, scanned)) return rc;
   return flat_search_impl(xb, dtype, scanned, dim, xq, nq, k, D, I, 0, ws, ws_bytes, route_mask, mask_stride, nullptr, stream, &h);
+}
+
+int rr_flat_search_segments_l2(const void* xb, const float* half_sqnorm, int dtype, int64_t n_rows_total, int dim, const rr_segment* segs,
+                               int n_segs, const void* xq, int nq, int k, float* D, int64_t* I, void* ws, size_t ws_bytes,
+                               const uint8_t* route_mask, int64_t mask_stride, void* stream) {
+  if (!rr::half_dtype(dtype)) return fail(RR_ERR_INVALID, "rr_flat_search_segments_l2: bad dtype%s");
+  rr::SegHost h;
+  int64_t scanned = 0;
+  if (int rc = seg_host_from(segs, n_segs, n_rows_total, route_mask, mask_stride, "rr_flat_search_segments_l2", h, scanned)) return rc;
+  if (int rc = check_search_sizes(dtype, scanned, dim, nq, k)) return rc;
+  if (nq == 0) return RR_OK;
+  if (!half_sqnorm && scanned > 0) return fail(RR_ERR_INVALID, "rr_flat_search_segments_l2: null half_sqnorm%s");
+  // a federation without rows has no norms to pass; any non-null marker selects the L2 finalize (padding +inf), never dereferenced
+  static const float kEmpty = 0.f;
+  return flat_search_impl(xb, dtype, scanned, dim, xq, nq, k, D, I, 0, ws, ws_bytes, route_mask, mask_stride,
+                          half_sqnorm ? half_sqnorm : &kEmpty, stream, &h);
 }
 
 // ---- f32-faithful exact search -----------------------------------------------------------------------------------------

@@ -33,7 +33,9 @@ namespace rr {
 
 // L2 = true ranks by  q.x - |x|^2/2  (descending == ascending squared L2 distance): the per-row |x|^2/2 of a tile is
 // one more 256-byte LDS-DMA piece (issued by wave 0, ahead of the tile-after-next's pieces so the in-order vmcnt wait of
-// the tile covers it) and the epilogue subtracts it before the filter.
+// the tile covers it) and the epilogue subtracts it before the filter.  L2 and SEG combine (rr_flat_search_segments_l2): the
+// norms are those of the tile the DMA stream's cursor maps the ordinal to (issue_norms); slot, wait counts and ring depth are
+// the plain L2 kernel's.
 // SEG = true: the launch is a chunk of a segmented search (a.ranges: one run of tiles per segment, a TileCursor per stream).  Plain
 // searches run the SEG = false instantiation, whose tile arithmetic and epilogue carry nothing of that (round 4: the same-device
 // A/B against round 2's kernel priced the run-time form at 0.5 - 0.8 % of the headline's scan launch, profiles/r04/headline_ab.json).
@@ -88,10 +90,13 @@ __global__ __launch_bounds__(256, 1) void flat_scan16_kernel(const ScanArgs a) {
   const int nblk = ((int)a.nq + 15) >> 4;
   const int nb = __builtin_amdgcn_readfirstlane(nblk > wave ? (nblk - wave + 3) >> 2 : 0);
 
-  // L2: |x|^2/2 of the 32 rows of tile ordinal jj -> LDS floats [NS*TILE_BYTES + slot*256 ...] (lanes 32..63 duplicate)
-  auto issue_norms = [&](uint32_t jj, int slot_) {   // (L2 metric: never a segmented search, no cursor)
+  // L2: |x|^2/2 of the 32 rows of tile ordinal jj -> LDS floats [NS*TILE_BYTES + slot*256 ...] (lanes 32..63 duplicate).
+  // Segmented search: the tile is the one the DMA stream's cursor maps jj to - every call follows tile_src(jj) of the same ordinal on
+  // the same wave, so dcur already stands in jj's run and the norm stream needs no cursor of its own (wave-uniform like the corpus
+  // pieces: one scalar add).  Rows past the last scanned row (the pad of a chunk's last run) clamp like the corpus rows do.
+  auto issue_norms = [&](uint32_t jj, int slot_) {
     if (jj >= a.n_tiles) jj = a.n_tiles - 1;
-    uint32_t row = (a.tile_first + jj * a.tile_stride) * kTileRows + (lane & 31);
+    uint32_t row = (a.tile_first + jj * a.tile_stride + (SEG ? (uint32_t)dcur.delta : 0u)) * kTileRows + (lane & 31);
     row = row < a.n_rows ? row : a.n_rows - 1;
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.half_sqnorm + row),
                                      (__attribute__((address_space(3))) void*)(smem + NS * TILE_BYTES + slot_ * 256), 4, 0, 0);
@@ -470,8 +475,10 @@ static hipError_t launch_scan16(const ScanArgs& a, int grid, hipStream_t st) {
 template <typename T, int D>
 static hipError_t launch_scan_t(const ScanArgs& a, bool dense, int grid, hipStream_t st) {
   const bool nt = (size_t)a.n_rows * D * 2 > kNtThresholdBytes;
-  if (a.ranges) {       // chunk launch of a segmented search (inner product, filter launches only)
-    if (a.half_sqnorm || dense) return hipErrorNotSupported;
+  if (a.ranges) {       // chunk launch of a segmented search (filter launches only: its sample and dense launches carry no ranges)
+    if (dense) return hipErrorNotSupported;
+    if (a.half_sqnorm)  // ... under the L2 metric: the norm stream follows the DMA stream's cursor
+      return nt ? launch_scan16<T, D, false, true, true, true>(a, grid, st) : launch_scan16<T, D, false, false, true, true>(a, grid, st);
     return nt ? launch_scan16<T, D, false, true, false, true>(a, grid, st) : launch_scan16<T, D, false, false, false, true>(a, grid, st);
   }
   if (a.half_sqnorm) {  // L2 metric

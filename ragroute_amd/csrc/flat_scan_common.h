@@ -225,6 +225,20 @@ __device__ __forceinline__ void lane_state_segments_init(const ScanArgs& a, Lane
 
 __device__ __forceinline__ float max4v(const f32x4& v) { return max4(v[0], v[1], v[2], v[3]); }
 
+// Segmented search, epilogue stream: the wave enters another segment's slice at launch ordinal j (wave-uniform, once per segment and
+// launch) - the slice's valid-row limit and its thresholds (+inf for queries not routed to it) replace the lane's.  NQB / QPW / DEAL /
+// qw as tile_epilogue16, which calls this; the wide-row kernels' segmented L2 forms call it ahead of the epilogue, because the norms
+// they subtract first belong to the tile this cursor maps j to.
+template <int NQB, int QPW, bool DEAL>
+__device__ __forceinline__ void epilogue_enter_segment(const ScanArgs& a, LaneState4& st, uint32_t j, int col, int qw) {
+  const RangeEntry e = cursor_advance(a, st.cur, j);
+  st.row_limit = e.row_limit;
+  uint32_t qi[4];
+#pragma unroll
+  for (int qb = 0; qb < 4; ++qb) qi[qb] = DEAL ? (qb * 4 + qw) * 16 + col : qw * QPW + (qb < NQB ? qb : 0) * 16 + col;
+  load_thresholds<NQB>(a, e.seg, qi, st.thr);
+}
+
 // INLINE_COMPACT: no function call in the slow path (for kernels that keep asynchronously loaded registers live across it)
 // QPW: queries per wave (the wave's queries are wave * QPW + qb * 16 + col); WAVES: waves per workgroup (compaction scratch slots);
 // DEAL: the query blocks are dealt round robin instead (slot qb of wave w = block 4 qb + w: flat_scan16_kernel)
@@ -246,15 +260,8 @@ __device__ __forceinline__ void tile_epilogue16(const ScanArgs& a, LaneState4& s
     }
     return;
   }
-  if (SEG && j >= st.cur.j_end) {   // segmented search only (plain: j_end = ~0); wave-uniform, once per segment and launch: the wave enters
-    // another segment's slice - its valid-row limit and its thresholds (+inf for queries not routed to it) replace the lane's
-    const RangeEntry e = cursor_advance(a, st.cur, j);
-    st.row_limit = e.row_limit;
-    uint32_t qi[4];
-#pragma unroll
-    for (int qb = 0; qb < 4; ++qb) qi[qb] = DEAL ? (qb * 4 + qw) * 16 + col : qw * QPW + (qb < NQB ? qb : 0) * 16 + col;
-    load_thresholds<NQB>(a, e.seg, qi, st.thr);
-  }
+  // segmented search only (plain: j_end = ~0); a no-op where the caller has entered the slice already (segmented L2, wide rows)
+  if (SEG && j >= st.cur.j_end) epilogue_enter_segment<NQB, QPW, DEAL>(a, st, j, col, qw);
   const uint32_t tile = a.tile_first + j * a.tile_stride + (SEG ? (uint32_t)st.cur.delta : 0u);
   float gm[2][4];
   bool hit = false;

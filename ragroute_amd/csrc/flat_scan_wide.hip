@@ -6,6 +6,7 @@
 //                             8 waves = 2 row halves x 4 query quarters, the query columns of a K step DMA'd into LDS once per CU
 //   flat_scan_wide8_kernel    d <= 2048, up to 208 queries: 8 waves, queries streamed into registers
 //   flat_scan_wide_pd_kernel  d > 2048 up to 192 queries, 9 / 11 / 12 query blocks at d <= 2048, every dense (sample) launch: 4 waves
+//   ... <..., SEGL2 = true>   the same three for the chunk launches of a segmented L2 search (norms under the epilogue's cursor)
 // What the three share is defined once, ahead of them: the fixed-AGPR accumulator access (RR_ASM_FIXED_ACC, Mfma16Fixed,
 // read_acc_fixed), the K rotation, the L2 epilogue step (subtract_half_sqnorms) and, for the pd and wide8 kernels, the query
 // prefetch discipline (pin_query_buffers, load_queries, closing_wait, dispatch_step, drain_query_buffers).  The LDS image of a
@@ -108,11 +109,14 @@ __device__ __forceinline__ int wide_group_rotation(const ScanArgs& a, uint32_t g
 }
 __device__ __forceinline__ int wide_rotated(int kg, int rot, int KG) { return kg + rot >= KG ? kg + rot - KG : kg + rot; }
 
-// L2 metric: rank by q.x - |x|^2/2.  Subtracts the half squared norms of the lane's 2 x 4 rows of tile ordinal j from its NQB
-// accumulator blocks (an L2 search is never segmented: no cursor; rows past the end are clamped here and filtered by id later).
+// L2 metric: rank by q.x - |x|^2/2.  Subtracts the half squared norms of the lane's 2 x 4 rows of `tile` from its NQB accumulator
+// blocks.  `tile` is the tile of the MATRIX: tile_first + j * tile_stride of a plain launch, the tile the epilogue's cursor maps
+// ordinal j to in a chunk of a segmented search (the SEGL2 forms of the kernels below).  Rows past the last scanned row (a.n_rows:
+// the end of a plain corpus, the end of the last segment's valid rows) are clamped here and filtered by id later; gap rows of a
+// segmented matrix have norms of their own, unspecified like the rows, and fail the row-validity test of the epilogue.
 template <int NQB>
-__device__ __forceinline__ void subtract_half_sqnorms(const ScanArgs& a, uint32_t j, int g, f32x4 (&e)[2][4]) {
-  const uint32_t r0 = (a.tile_first + j * a.tile_stride) * kTileRows + 4 * g;
+__device__ __forceinline__ void subtract_half_sqnorms(const ScanArgs& a, uint32_t tile, int g, f32x4 (&e)[2][4]) {
+  const uint32_t r0 = tile * kTileRows + 4 * g;
   f32x4 h0, h1;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -218,8 +222,14 @@ __device__ __forceinline__ void drain_query_buffers(F (&q)[QB][NQB][2]) {
 }
 // DENSE launches (bootstrap sample, corpora <= 8192 rows) cover at most 256 tiles: with 8-tile groups only 32 workgroups would
 // have work and each would still walk the whole K loop (112 us at d = 4096), so they use one tile per group.
-template <typename T, bool DENSE, bool L2, int NQB>
+// SEGL2 (the last template argument of the three kernels of this file) = true compiles the chunk launch of a segmented L2 search
+// (rr_flat_search_segments_l2: a.ranges and a.half_sqnorm together) as instantiations of their own, so that the plain L2 and the
+// segmented inner-product instantiations (SEGL2 = false) stay the code they were.  What SEGL2 adds is in the tile epilogue only: the
+// wave enters a segment's slice (epilogue_enter_segment: row limit, thresholds) BEFORE the norms are subtracted, and the norms are
+// those of the tile the epilogue's cursor maps the ordinal to.
+template <typename T, bool DENSE, bool L2, int NQB, bool SEGL2 = false>
 __global__ __launch_bounds__(256, 1) void flat_scan_wide_pd_kernel(const ScanArgs a, const int D) {
+  static_assert(!SEGL2 || (L2 && !DENSE), "a segmented L2 chunk launch is an L2 filter launch");
   typedef typename Mfma<T>::frag frag;
   constexpr int PD = 2;                    // K steps the queries are prefetched ahead
   constexpr int NT = DENSE ? 1 : 8;        // 32-row tiles per group
@@ -405,7 +415,12 @@ __global__ __launch_bounds__(256, 1) void flat_scan_wide_pd_kernel(const ScanArg
         if (j < n_tiles) {
           f32x4 e[2][4];
           read_tile(std::integral_constant<int, 32 * t>{}, e);
-          if (L2) subtract_half_sqnorms<NQB>(a, j, g, e);
+          if constexpr (SEGL2) {
+            if (j >= st.cur.j_end) epilogue_enter_segment<NQB, QPW, false>(a, st, j, col, wave);
+            subtract_half_sqnorms<NQB>(a, a.tile_first + j * a.tile_stride + (uint32_t)st.cur.delta, g, e);
+          } else if (L2) {
+            subtract_half_sqnorms<NQB>(a, a.tile_first + j * a.tile_stride, g, e);
+          }
           tile_epilogue16<DENSE, NQB, QPW, true, 4>(a, st, e, j, lane, wave);
         }
       });
@@ -432,8 +447,9 @@ __global__ __launch_bounds__(256, 1) void flat_scan_wide_pd_kernel(const ScanArg
 // LDS image, same ring and queue discipline as above with 4 DMA pieces and 4 query loads per wave and step; every A fragment
 // is read from LDS by 8 waves instead of 4 (256 KB per step and CU = half of the LDS read rate).
 
-template <typename T, bool L2, int NQB>
+template <typename T, bool L2, int NQB, bool SEGL2 = false>
 __global__ __launch_bounds__(512) void flat_scan_wide8_kernel(const ScanArgs a, const int D) {
+  static_assert(!SEGL2 || L2, "a segmented L2 chunk launch is an L2 launch");
   typedef typename Mfma<T>::frag frag;
   constexpr int PD = 2;                    // K steps the queries are prefetched ahead
   constexpr int NT = 8;                    // 32-row tiles per group
@@ -587,7 +603,12 @@ __global__ __launch_bounds__(512) void flat_scan_wide8_kernel(const ScanArgs a, 
             e[0][qb] = read_acc_fixed<128, 16 * t + 4 * qb>();
             e[1][qb] = read_acc_fixed<128, 16 * t + 8 + 4 * qb>();
           });
-          if (L2) subtract_half_sqnorms<NQB>(a, j, g, e);
+          if constexpr (SEGL2) {
+            if (j >= st.cur.j_end) epilogue_enter_segment<NQB, QPW, false>(a, st, j, col, wave);
+            subtract_half_sqnorms<NQB>(a, a.tile_first + j * a.tile_stride + (uint32_t)st.cur.delta, g, e);
+          } else if (L2) {
+            subtract_half_sqnorms<NQB>(a, a.tile_first + j * a.tile_stride, g, e);
+          }
           tile_epilogue16<false, NQB, QPW, true, 8>(a, st, e, j, lane, wave);
         }
       });
@@ -612,9 +633,10 @@ __global__ __launch_bounds__(512) void flat_scan_wide8_kernel(const ScanArgs a, 
 // HBM latency), queries 2 slots (one step ahead: they come from L2) = all 160 KB of LDS.  Two waves share each query, so a
 // workgroup owns 8 candidate buffers per query (row half x lane quarter).
 // L2 = true (round 4): ranks by q.x - |x|^2/2 like the other kernels' L2 forms - the epilogue subtracts the rows' half squared norms
-// (a.half_sqnorm) from the accumulators before the filter; an L2 search is never segmented.
-template <typename T, bool L2 = false>
+// (a.half_sqnorm) from the accumulators before the filter; SEGL2: the chunk launch of a segmented L2 search (see flat_scan_wide_pd_kernel).
+template <typename T, bool L2 = false, bool SEGL2 = false>
 __global__ __launch_bounds__(512) void flat_scan_wide_rs_kernel(const ScanArgs a, const int D) {
+  static_assert(!SEGL2 || L2, "a segmented L2 chunk launch is an L2 launch");
   typedef typename Mfma<T>::frag frag;
   constexpr int NT = 8;                    // 32-row tiles per group (256 rows)
   constexpr int SLAB = NT * 4096;          // one K step of 256 rows (or of the 256 queries) in LDS
@@ -788,7 +810,12 @@ __global__ __launch_bounds__(512) void flat_scan_wide_rs_kernel(const ScanArgs a
           e[0][qb] = read_acc_fixed<128, 4 * ((2 * t) * 4 + qb)>();
           e[1][qb] = read_acc_fixed<128, 4 * ((2 * t + 1) * 4 + qb)>();
         });
-        if (L2) subtract_half_sqnorms<4>(a, j, g, e);
+        if constexpr (SEGL2) {
+          if (j >= st.cur.j_end) epilogue_enter_segment<4, 64, false>(a, st, j, col, qq);
+          subtract_half_sqnorms<4>(a, a.tile_first + j * a.tile_stride + (uint32_t)st.cur.delta, g, e);
+        } else if (L2) {
+          subtract_half_sqnorms<4>(a, a.tile_first + j * a.tile_stride, g, e);
+        }
         tile_epilogue16<false, 4, 64, true, 8>(a, st, e, j, lane, wave, qq);
       }
     });
@@ -847,15 +874,20 @@ static hipError_t launch_scan_wide_t(const ScanArgs& a, const ScanPlan& p, bool 
   if (D % 128 != 0) return hipErrorInvalidValue;
   const size_t lds = (size_t)4 * (dense ? 1 : 8) * 4096;   // prefetch distance 2: a ring of 4 slots
   const bool l2 = a.half_sqnorm != nullptr, one8 = nqb4 == 1;
+  const bool segl2 = l2 && a.ranges != nullptr && !dense;   // chunk launch of a segmented L2 search (its sample / dense launches carry no ranges)
 #define RR_LAUNCH_PD(DENSE_, L2_, NQB_) return launch_with_lds(flat_scan_wide_pd_kernel<T, DENSE_, L2_, NQB_>, grid, 256, lds, st, a, D);
   if (!dense && p.kernel == ScanKernel::kWideRs) {
     const size_t lds_rs = (size_t)5 * 8 * 4096;   // 3 corpus + 2 query slots of 32 KB: all 160 KB
-    if (l2 && a.ranges) return hipErrorNotSupported;
+    if (segl2) return launch_with_lds(flat_scan_wide_rs_kernel<T, true, true>, grid, 512, lds_rs, st, a, D);
     if (l2) return launch_with_lds(flat_scan_wide_rs_kernel<T, true>, grid, 512, lds_rs, st, a, D);
     return launch_with_lds(flat_scan_wide_rs_kernel<T, false>, grid, 512, lds_rs, st, a, D);
   }
   if (!dense && p.kernel == ScanKernel::kWide8) {
 #define RR_LAUNCH_8(L2_, NQB_) return launch_with_lds(flat_scan_wide8_kernel<T, L2_, NQB_>, grid, 512, lds, st, a, D);
+    if (segl2) {
+      if (one8) return launch_with_lds(flat_scan_wide8_kernel<T, true, 1, true>, grid, 512, lds, st, a, D);
+      return launch_with_lds(flat_scan_wide8_kernel<T, true, 2, true>, grid, 512, lds, st, a, D);
+    }
     if (l2) { if (one8) RR_LAUNCH_8(true, 1) else RR_LAUNCH_8(true, 2) }
     if (one8) RR_LAUNCH_8(false, 1) else RR_LAUNCH_8(false, 2)
 #undef RR_LAUNCH_8
@@ -866,6 +898,12 @@ static hipError_t launch_scan_wide_t(const ScanArgs& a, const ScanPlan& p, bool 
     if (nqb4 == 2) RR_LAUNCH_PD(DENSE_, L2_, 2)          \
     if (nqb4 == 3) RR_LAUNCH_PD(DENSE_, L2_, 3)          \
     RR_LAUNCH_PD(DENSE_, L2_, 4)                         \
+  }
+  if (segl2) {
+    if (nqb4 == 1) return launch_with_lds(flat_scan_wide_pd_kernel<T, false, true, 1, true>, grid, 256, lds, st, a, D);
+    if (nqb4 == 2) return launch_with_lds(flat_scan_wide_pd_kernel<T, false, true, 2, true>, grid, 256, lds, st, a, D);
+    if (nqb4 == 3) return launch_with_lds(flat_scan_wide_pd_kernel<T, false, true, 3, true>, grid, 256, lds, st, a, D);
+    return launch_with_lds(flat_scan_wide_pd_kernel<T, false, true, 4, true>, grid, 256, lds, st, a, D);
   }
   if (l2) {
     if (dense) RR_LAUNCH_PD_N(true, true)

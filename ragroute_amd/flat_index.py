@@ -429,11 +429,16 @@ class SegmentedIndex(_Faithful):
     Source s occupies rows [begin_s, begin_s + n_s) of the matrix, begin_s a multiple of 256; `source(s)` is a FlatIndex on that
     slice (no copy), so the per-source call surface (`DataSource.retrieve_docs_*`) keeps working on the same memory.
     Result ids are id_offsets[s] + local row; ties are broken by (source order, row) = ascending id when the id offsets ascend.
-    Metrics: "ip" / "cosine".  exact_f32=True: f32 rows beside the half matrix, results faithful to them (FlatIndex)."""
+    Metrics: "ip" / "cosine", and "l2" (C ABI `rr_flat_search_segments_l2`: squared L2 distances, nearest first, padding
+    (+inf, -1) — the reference's wikipedia federation, ten sources of one DPR encoder whose merge keeps the lowest scores,
+    config.py:59-70, rerank.py:28-34); `_hn` then holds |x|^2 / 2 of every matrix row, filled source by source.
+    exact_f32=True (ip / cosine): f32 rows beside the half matrix, results faithful to them (FlatIndex)."""
 
     def __init__(self, d, rows_per_source, id_offsets=None, mask_cols=None, metric="ip", dtype="fp16", device=None, exact_f32=False):
-        if metric not in ("ip", "cosine"):
-            raise ValueError("SegmentedIndex serves the ip / cosine metrics")
+        if metric not in ("ip", "cosine", "l2"):
+            raise ValueError(f"unknown metric {metric!r}")
+        if exact_f32 and metric == "l2":
+            raise ValueError("exact_f32 serves the ip / cosine metrics only")
         rows = [int(n) for n in rows_per_source]
         if not 1 <= len(rows) <= _lib.RR_MAX_SEGMENTS or min(rows) < 0:
             raise ValueError(f"need 1 .. {_lib.RR_MAX_SEGMENTS} sources with >= 0 rows each")
@@ -456,6 +461,8 @@ class SegmentedIndex(_Faithful):
         self._segs = (_lib.SegmentStruct * len(rows))(*[_lib.SegmentStruct(b, n, o, c, 0)
                                                         for b, n, o, c in zip(self.begins, rows, self.id_offsets, self.mask_cols)])
         self.ntotal = sum(rows)
+        # metric "l2": |x|^2 / 2 of every matrix row, aligned with _xb (alignment gaps: unspecified, never used)
+        self._hn = torch.zeros(max(1, self.n_rows_total), dtype=torch.float32, device=self.device) if metric == "l2" else None
         self.exact_f32 = bool(exact_f32)
         if self.exact_f32:
             self._faithful_init(self.n_rows_total)
@@ -464,11 +471,29 @@ class SegmentedIndex(_Faithful):
         """Device view [n_s, dim] of source s (fill it with rows in the index dtype, zero padded to dim)."""
         return self._xb[self.begins[s]: self.begins[s] + self.rows[s]]
 
+    def norms_of(self, s):
+        """Metric "l2": device view [n_s] of source s's half squared norms."""
+        return self._hn[self.begins[s]: self.begins[s] + self.rows[s]]
+
+    def refresh_norms(self, s):
+        """Metric "l2": recompute source s's half squared norms from its stored rows (fill() does; call it after writing
+        rows_of(s) directly)."""
+        if self.metric != "l2" or self.rows[s] == 0:
+            return
+        with torch.cuda.device(self.device):
+            check(lib().rr_half_sqnorms(self.rows_of(s).data_ptr(), _RR_DTYPE[self.dtype], self.rows[s], self.dim,
+                                        self.norms_of(s).data_ptr(), _stream_ptr()), "rr_half_sqnorms")
+
+    def _point_at(self, idx, s):
+        """Make FlatIndex idx a view of source s: its rows and, for "l2", its slice of the norms (nothing is recomputed)."""
+        idx._xb, idx.ntotal = self.rows_of(s), self.rows[s]
+        idx._x8 = idx._x8_stats = None
+        idx._hn = self.norms_of(s) if self.metric == "l2" and self.rows[s] else None
+        return idx
+
     def source(self, s):
         """FlatIndex over source s's slice of the matrix (no copy): the per-source search surface on the same memory."""
-        idx = FlatIndex(self.d, metric=self.metric, dtype=self.dtype, device=self.device)
-        idx.adopt(self.rows_of(s))
-        return idx
+        return self._point_at(FlatIndex(self.d, metric=self.metric, dtype=self.dtype, device=self.device), s)
 
     def fill(self, s, x, chunk_rows=1 << 18):
         """Ingest float32 rows [n_s, d] (numpy or tensor) into source s (normalised for cosine)."""
@@ -488,6 +513,7 @@ class SegmentedIndex(_Faithful):
                 part = part.to(self.device, dtype=torch.float32).contiguous()
                 check(lib().rr_rows_to_half(part.data_ptr(), part.shape[0], self.d, self.d, out[b: b + part.shape[0]].data_ptr(),
                                             _RR_DTYPE[self.dtype], self.dim, int(self.metric == "cosine"), _stream_ptr()), "rr_rows_to_half")
+        self.refresh_norms(s)
 
     @classmethod
     def from_indexes(cls, indexes, id_offsets=None, mask_cols=None):
@@ -499,8 +525,12 @@ class SegmentedIndex(_Faithful):
                 raise ValueError("sources of one SegmentedIndex share dimension, metric, dtype and device")
         seg = cls(first.d, [i.ntotal for i in indexes], id_offsets, mask_cols, first.metric, first.dtype, first.device)
         for s, i in enumerate(indexes):
+            if i.exact_f32:
+                raise _lib.RagrouteHipError("from_indexes() packs half matrices only; an exact_f32 index ingests its f32 rows with fill()")
             seg.rows_of(s).copy_(i.xb)
-            i.adopt(seg.rows_of(s))
+            if first.metric == "l2" and i.ntotal:
+                seg.norms_of(s).copy_(i._hn[: i.ntotal])
+            seg._point_at(i, s)
         return seg
 
     def prepare_queries(self, xq):
@@ -522,6 +552,12 @@ class SegmentedIndex(_Faithful):
         else:
             D, I = out
         mptr, mstride = self._mask_args(route_mask, nq)
+        if self.metric == "l2":
+            check(lib().rr_flat_search_segments_l2(self._xb.data_ptr(), self._hn.data_ptr(), _RR_DTYPE[self.dtype], self.n_rows_total,
+                                                   self.dim, self._segs, len(self.rows), xq_half.data_ptr(), nq, k, D.data_ptr(),
+                                                   I.data_ptr(), ws.data_ptr(), ws.numel(), mptr, mstride, _stream_ptr()),
+                  "rr_flat_search_segments_l2")
+            return D, I
         check(lib().rr_flat_search_segments(self._xb.data_ptr(), _RR_DTYPE[self.dtype], self.n_rows_total, self.dim, self._segs,
                                             len(self.rows), xq_half.data_ptr(), nq, k, D.data_ptr(), I.data_ptr(), ws.data_ptr(),
                                             ws.numel(), mptr, mstride, _stream_ptr()), "rr_flat_search_segments")

@@ -22,9 +22,13 @@ class RetrievalPipeline:
         ranks (default: agreed on by one all_reduce at the first search).
         share_queries: optional list, one hashable key per shard — shards with the same key receive the SAME query
         embeddings (the key is the encoder: config.py:37-71; MedRAG's four sources all use MedCPT, five FeB4RAG sources
-        UAE-Large-V1).  Local shards that share a key, dimension, metric and dtype are packed into one SegmentedIndex and
-        searched in ONE pass (`rr_flat_search_segments`) whose result is already their merged top-k: one exchange slot per
-        group instead of one per shard.  The shard objects are re-pointed at their slices of the packed matrix.
+        UAE-Large-V1, the ten wikipedia sources one DPR encoder).  Local shards that share a key, dimension, metric and dtype are
+        packed into one SegmentedIndex and searched in ONE pass (`rr_flat_search_segments`, `rr_flat_search_segments_l2`) whose
+        result is already their merged top-k: one exchange slot per group instead of one per shard.  The shard objects are
+        re-pointed at their slices of the packed matrix.
+        Every unit of a pipeline ranks the same way: all "l2" (distances: the merge keeps the LOWEST, rerank.py:28-34, and unused
+        exchange slots are padded with +inf) or none (scores: the highest, padding -inf); a mix raises ValueError, because a
+        distance and an inner product cannot be merged.
         units: alternatively, the search units themselves — a list of (FlatIndex | SegmentedIndex, [source ids]) built by the
         caller (a SegmentedIndex filled in place never holds its sources twice)."""
         if len(shards) != len(shard_ids):
@@ -52,7 +56,7 @@ class RetrievalPipeline:
             from .flat_index import SegmentedIndex
             groups = {}
             for idx, sid, key in zip(self.shards, self.shard_ids, share_queries):
-                if getattr(idx, "metric", None) in ("ip", "cosine"):
+                if getattr(idx, "metric", None) in ("ip", "cosine", "l2"):
                     groups.setdefault((key, idx.d, idx.metric, idx.dtype), []).append((sid, idx))
                 else:
                     self.units.append(("shard", idx, [sid], sid << SHARD_SHIFT))
@@ -65,6 +69,10 @@ class RetrievalPipeline:
                     seg = SegmentedIndex.from_indexes([m[1] for m in members], id_offsets=[s << SHARD_SHIFT for s in sids], mask_cols=sids)
                     self.units.append(("segments", seg, sids, None))
             self.units.sort(key=lambda u: u[2][0])
+        l2 = {getattr(u[1], "metric", "ip") == "l2" for u in self.units}
+        if len(l2) > 1:
+            raise ValueError("a pipeline's units must all be \"l2\" or all ip / cosine: distances and scores cannot be merged")
+        self.descending = l2 != {True}     # the merge direction and the padding of the exchange slots follow the units' metric
         self.stage_events = None   # measurement aid (bench.py): [(exchange start, exchange end = merge start, merge end)] per search
 
     @classmethod
@@ -103,6 +111,7 @@ class RetrievalPipeline:
                     for j, sl in enumerate(slices):
                         if fill_half is not None:
                             fill_half(placement.sources[sl.sid], sl, seg.rows_of(j))
+                            seg.refresh_norms(j)
                         elif sl.n_rows:
                             seg.fill(j, rows_f32(sl.sid, sl.row_begin, sl.row_begin + sl.n_rows))
                     units.append((seg, [sl.sid for sl in slices]))
@@ -146,7 +155,7 @@ class RetrievalPipeline:
             raise ValueError(f"{len(self.units)} local search units but only {self.slots} exchange slots")
         key = (B, k)
         if key not in self._packed:
-            buf, D, I = alloc_packed(B, k, device, self.slots)
+            buf, D, I = alloc_packed(B, k, device, self.slots, float("-inf") if self.descending else float("inf"))
             if self.slots == 1:
                 D, I = D[None], I[None]
             self._packed = {key: (buf, D, I)}
@@ -180,12 +189,12 @@ class RetrievalPipeline:
                                     route_mask=None if mask is None else mask[:, sids[0]])
         if self.stage_events is None:
             out = exchange_packed(buf, self.group, self._gathered)       # C1: the ONE collective
-            return merge_gathered(out, B, k, self.slots, k, True)        # K4, reading the gathered buffer where it lies
+            return merge_gathered(out, B, k, self.slots, k, self.descending)   # K4, reading the gathered buffer where it lies
         e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
         e0.record()
         out = exchange_packed(buf, self.group, self._gathered)
         e1.record()
-        res = merge_gathered(out, B, k, self.slots, k, True)
+        res = merge_gathered(out, B, k, self.slots, k, self.descending)
         e2.record()
         self.stage_events.append((e0, e1, e2, e_start))
         return res

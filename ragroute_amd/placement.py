@@ -143,7 +143,7 @@ def _ordered(sources):
     return [sorted(members, key=lambda m: m.sid) for members in order]
 
 
-def _pour(groups, G, cap, cost, min_slice):
+def _pour(groups, G, cap, cost, min_slice, group_l2=False):
     """Fill ranks 0 .. G-1 in order up to `cap` ms each.  Returns (per-rank {group key: [RowSlice]}, per-rank ms), or None
     if the federation does not fit under this cap."""
     ranks = [dict() for _ in range(G)]
@@ -154,8 +154,8 @@ def _pour(groups, G, cap, cost, min_slice):
             begin, per_row = 0, cost.row_ms(src)
             while True:
                 remaining = src.rows - begin
-                # no segmented L2 search: every piece of an L2 source is a unit of its own
-                key = src.group if src.metric != "l2" else src.group + (src.sid, begin)
+                # group_l2=False (the layout before rr_flat_search_segments_l2): every piece of an L2 source is a unit of its own
+                key = src.group if src.metric != "l2" or group_l2 else src.group + (src.sid, begin)
                 opening = cost.segment_ms if key in ranks[r] else cost.fixed_ms
                 fit = int(max(0.0, cap - load[r] - opening) / per_row)
                 if remaining == 0 or fit >= remaining:
@@ -184,9 +184,12 @@ def _pour(groups, G, cap, cost, min_slice):
     return ranks, load
 
 
-def plan(sources, G, cost=None, min_slice_rows=MIN_SLICE_ROWS):
+def plan(sources, G, cost=None, min_slice_rows=MIN_SLICE_ROWS, group_l2=False):
     """sources: iterable of Source; G: number of GPUs.  Returns a Placement whose largest predicted per-rank time is minimal
-    for this pouring order (bisection on the cap; at most G - 1 cuts, each on a 256-row boundary)."""
+    for this pouring order (bisection on the cap; at most G - 1 cuts, each on a 256-row boundary).
+    group_l2: the "l2" sources of one group share search units and are cut into row slices like ip / cosine ones (one
+    rr_flat_search_segments_l2 per rank and group: the reference's wikipedia federation, ten sources of one DPR encoder);
+    False keeps every piece of an L2 source a unit of its own."""
     sources = list(sources)
     if G < 1:
         raise ValueError("need at least one GPU")
@@ -199,14 +202,14 @@ def plan(sources, G, cost=None, min_slice_rows=MIN_SLICE_ROWS):
     groups = _ordered(sources)
     total = sum(cost.row_ms(s) * s.rows for s in sources) + cost.fixed_ms * len(groups)
     lo, hi = total / G, total + cost.fixed_ms * len(sources) + 1e-9
-    best = _pour(groups, G, hi, cost, min_slice_rows)
+    best = _pour(groups, G, hi, cost, min_slice_rows, group_l2)
     if best is None:
         raise RuntimeError("placement: the one-rank cap does not fit (cost model inconsistent)")
     for _ in range(48):
         if hi - lo < 1e-5 * hi:
             break
         mid = 0.5 * (lo + hi)
-        got = _pour(groups, G, mid, cost, min_slice_rows)
+        got = _pour(groups, G, mid, cost, min_slice_rows, group_l2)
         if got is None:
             lo = mid
         else:

@@ -48,17 +48,18 @@ def gather_candidates(D, I, group=None):
             Ig.view(world, B, k).permute(1, 0, 2).reshape(B, world * k))
 
 
-def alloc_packed(B, k, device, slots=1):
+def alloc_packed(B, k, device, slots=1, fill=float("-inf")):
     """One allocation holding D f32[slots,B,k] followed by I i64[slots,B,k] (one slot per local shard): the scan kernels
     write straight into the views and the exchange moves the whole buffer with ONE collective.  Every slot starts as
-    padding (-inf, -1), so a rank with fewer shards than `slots` contributes nothing for the unused ones.
+    padding (fill, -1) - fill = -inf for scores, +inf for the distances of "l2" units, whose merge is ascending - so a rank with
+    fewer shards than `slots` contributes nothing for the unused ones.
     Returns (buf, D, I); with slots == 1 the views are [B,k]."""
     nD = slots * B * k * 4
     pad = (-nD) % 8
     buf = torch.empty(nD + pad + slots * B * k * 8, dtype=torch.uint8, device=device)
     D = buf[:nD].view(torch.float32).view(slots, B, k)
     I = buf[nD + pad:].view(torch.int64).view(slots, B, k)
-    D.fill_(float("-inf"))
+    D.fill_(fill)
     I.fill_(-1)
     return (buf, D[0], I[0]) if slots == 1 else (buf, D, I)
 

@@ -2,7 +2,7 @@
 
     ragroute::flat_topk(xb, xq, k, id_offset=0, l2=False) -> (D f32[nq,k], I i64[nq,k])     index.search, data_source.py:158,186,203
     ragroute::l2_normalize_(x) -> x                                                         faiss.normalize_L2, data_source.py:199
-    ragroute::flat_topk_segments(xb, row_begins, rows, id_offsets, mask_cols, xq, k, route_mask=None) -> (D, I)
+    ragroute::flat_topk_segments(xb, row_begins, rows, id_offsets, mask_cols, xq, k, route_mask=None, l2=False, half_sqnorm=None) -> (D, I)
                                                                                             one search over the sources of one encoder
                                                                                             (config.py:37-71) = their per-source
                                                                                             index.search + http_server.py:280-293 + rerank.py:3-9
@@ -74,9 +74,12 @@ def _(xb, xq, k, id_offset=0, l2=False):
 
 @torch.library.custom_op("ragroute::flat_topk_segments", mutates_args=())
 def flat_topk_segments(xb: torch.Tensor, row_begins: list[int], rows: list[int], id_offsets: list[int], mask_cols: list[int],
-                       xq: torch.Tensor, k: int, route_mask: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+                       xq: torch.Tensor, k: int, route_mask: torch.Tensor | None = None, l2: bool = False,
+                       half_sqnorm: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
     """rr_flat_search_segments: xb ONE matrix [n, dim] holding source s at rows [row_begins[s], row_begins[s] + rows[s]) (begins
-    multiples of 256); route_mask optional bool/uint8 [nq, C], source s reads column mask_cols[s] (-1: always selected)."""
+    multiples of 256); route_mask optional bool/uint8 [nq, C], source s reads column mask_cols[s] (-1: always selected).
+    l2: rr_flat_search_segments_l2 instead (squared L2 distances, nearest first, padding +inf); half_sqnorm f32 [n] = |x|^2 / 2
+    of every matrix row (rr_half_sqnorms), computed here when it is not given."""
     n_seg = len(rows)
     if not (len(row_begins) == len(id_offsets) == len(mask_cols) == n_seg and 1 <= n_seg <= _lib.RR_MAX_SEGMENTS):
         raise ValueError("flat_topk_segments: one begin / row count / id offset / mask column per segment (1 .. 32 segments)")
@@ -95,7 +98,21 @@ def flat_topk_segments(xb: torch.Tensor, row_begins: list[int], rows: list[int],
             raise ValueError("flat_topk_segments: route_mask must be a bool/uint8 CUDA matrix [nq, C]")
         route_mask = route_mask.contiguous()
         mptr, mstride = route_mask.data_ptr(), route_mask.stride(0)
+    if half_sqnorm is not None and not l2:
+        raise ValueError("flat_topk_segments: half_sqnorm belongs to l2=True")
     with torch.cuda.device(xb.device):
+        if l2:
+            n = xb.shape[0]
+            if half_sqnorm is None:
+                half_sqnorm = torch.empty(max(1, n), dtype=torch.float32, device=xb.device)
+                check(lib().rr_half_sqnorms(xb.data_ptr(), _dtype_code(xb), n, xb.shape[1], half_sqnorm.data_ptr(), _stream()), "rr_half_sqnorms")
+            elif not (half_sqnorm.is_cuda and half_sqnorm.dtype == torch.float32 and half_sqnorm.dim() == 1 and half_sqnorm.shape[0] >= n):
+                raise ValueError("flat_topk_segments: half_sqnorm must be a float32 CUDA vector with one entry per matrix row")
+            half_sqnorm = half_sqnorm.contiguous()
+            check(lib().rr_flat_search_segments_l2(xb.data_ptr(), half_sqnorm.data_ptr(), _dtype_code(xb), n, xb.shape[1], segs, n_seg,
+                                                   xq.data_ptr(), nq, k, D.data_ptr(), I.data_ptr(), ws.data_ptr(), ws.numel(), mptr, mstride,
+                                                   _stream()), "rr_flat_search_segments_l2")
+            return D, I
         check(lib().rr_flat_search_segments(xb.data_ptr(), _dtype_code(xb), xb.shape[0], xb.shape[1], segs, n_seg, xq.data_ptr(), nq, k,
                                             D.data_ptr(), I.data_ptr(), ws.data_ptr(), ws.numel(), mptr, mstride, _stream()),
               "rr_flat_search_segments")
@@ -103,7 +120,7 @@ def flat_topk_segments(xb: torch.Tensor, row_begins: list[int], rows: list[int],
 
 
 @flat_topk_segments.register_fake
-def _(xb, row_begins, rows, id_offsets, mask_cols, xq, k, route_mask=None):
+def _(xb, row_begins, rows, id_offsets, mask_cols, xq, k, route_mask=None, l2=False, half_sqnorm=None):
     return xq.new_empty((xq.shape[0], k), dtype=torch.float32), xq.new_empty((xq.shape[0], k), dtype=torch.int64)
 
 
