@@ -80,7 +80,18 @@ size_t rr_flat_search_workspace_bytes_for(int k, int dim);
  *   d_xb     device [n_rows][dim] f16/bf16, dim == rr_padded_dim(d) (zero padded)
  *   d_xq     device [nq][dim] same dtype
  *   d_D      device f32 [nq][k]  scores (inner products, f32 accumulation) of the ROUNDED corpus and queries: the results are
- *            exact for the f16/bf16 copies; for the reference's f32 results see rr_flat_search_faithful below
+ *            exact for the f16/bf16 copies; for the reference's f32 results see rr_flat_search_faithful below.
+ *            fp16 SUBNORMAL rows and queries (|v| < 2^-14; unit-norm 768-wide embeddings hold about one per row) are ordinary
+ *            operands: measured on gfx950, the matrix cores take them unflushed and rr_rows_to_half keeps them, so scores of
+ *            rows m 2^-24, |m| <= 1023, equal the f64 oracle bit for bit in every scan kernel
+ *            (tests/test_wide_values_gpu.py::test_fp16_subnormal_rows_score_exactly).
+ *            Scores outside f32's range (bf16 rows reach them): a score is what f32 addition of the products gives - +inf or
+ *            -inf where the partial sums overflow, NaN where a stored value is NaN or +inf and -inf meet.  A NaN-scoring row is
+ *            never returned; rows scoring +inf come first (by ascending id), then the finite scores in order.  A REAL row that
+ *            scores -inf ranks with the (-inf, -1) padding, and which of the two a result's tail shows depends on the path: a
+ *            corpus of up to 8192 rows (the dense path) lists such rows after the finite ones as (-inf, id), by ascending id; a
+ *            larger corpus (chunk launches pass only scores strictly above a threshold that starts at -inf) never returns them
+ *            and pads with (-inf, -1) instead (tests/test_wide_values_gpu.py::test_scores_that_overflow_f32)
  *   d_I      device i64 [nq][k]  row ids + id_offset (shard base), or -1
  *   d_ws     device workspace of at least rr_flat_search_workspace_bytes(k) bytes
  *   d_route_mask  optional device u8, one byte per query at d_route_mask[q * mask_stride]: 0 means the router

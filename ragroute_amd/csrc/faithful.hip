@@ -123,7 +123,10 @@ __global__ __launch_bounds__(256) void faithful_queries_kernel(const float* __re
     const double dmax = __uint_as_float(stats[0]), xmax = __uint_as_float(stats[1]), hmax = __uint_as_float(stats[2]);
     const double en = sqrt(e2), hn = sqrt(h2);
     // 1.0001: the f64 roundings of the norms above (relative 1e-16 each); the last term: products of bf16 values that leave
-    // the f32 normal range (flushed to zero by the matrix cores), at most 2^-126 each
+    // the f32 normal range (flushed to zero by the matrix cores), at most 2^-126 each.  Subnormal fp16 INPUTS need no term: the
+    // matrix cores of gfx950 take them unflushed (measured: tests/test_wide_values_gpu.py::test_fp16_subnormal_rows_score_exactly is
+    // bit-exact on rows of subnormals, and tests/test_exact_f32_gpu.py's subnormal cases of test_eps_bounds_the_half_precision_scan
+    // hold with this bound), and an fp16 x fp16 product is at least 2^-48, far inside the f32 normal range
     double v = 1.0001 * (en * xmax + hn * dmax) + gamma * hn * hmax + (double)dim * 0x1p-120 * (1.0 + hn + hmax);
     if (hn * hmax > 1e37) v = __builtin_inf();
     eps[q] = up_f32(v);

@@ -33,17 +33,47 @@ def cases(seed, count, max_work=6e9, big=False):
     return out
 
 
-def run_case(c, dev, guard=True):
+WIDE_FAMILIES = ("rows", "queries", "balanced", "scaled")
+
+
+def wide_rng(c):
+    return np.random.default_rng([c["seed"], 0x51DE])
+
+
+def wide_family(c, metric, rng=None):
+    """The exact family of a case's wide-value run: the first draw of the case's wide stream (the l2 family under the L2 metric, after
+    the same draw, so that both metrics see the same stream)."""
+    i = int((rng if rng is not None else wide_rng(c)).integers(0, len(WIDE_FAMILIES)))
+    return "l2" if metric == "l2" else WIDE_FAMILIES[i]
+
+
+def case_data(c, rows, values, metric):
+    """(corpus f32 [rows, d] - rows: a count, or the list of a segmented case's sources - queries f32 [nq, d], rng) of a case.  values "small": int_data, drawn from the case's seed as ever.
+    "wide": one of tests/util.py's exact families (every stored mantissa bit in use; `scaled`: a power of two per row and query),
+    the l2 family under the L2 metric - family, values and exponents from a stream of their own derived from c["seed"], so that
+    the generators' case lists and the small-value data stay what they were."""
+    from tests.util import exact_case, int_data
+    if values == "small":
+        rng = np.random.default_rng(c["seed"])
+        parts = [int_data(rng, n, c["d"]) for n in (rows if isinstance(rows, list) else [rows])]     # one draw per source, as ever
+        return np.concatenate(parts), int_data(rng, c["nq"], c["d"]), rng
+    if values != "wide":
+        raise ValueError(f"values must be 'small' or 'wide', not {values!r}")
+    rng = wide_rng(c)
+    fam = wide_family(c, metric, rng)
+    xb, xq = exact_case(rng, sum(rows) if isinstance(rows, list) else rows, c["nq"], c["d"], fam, c["dtype"])
+    return xb, xq, rng
+
+
+def run_case(c, dev, guard=True, values="small"):
     """One case on integer data (exact scores: ids and scores must match the oracle bit for bit).  guard: corpus and
-    queries end on the last byte of their own device segment, so an out-of-range read faults."""
+    queries end on the last byte of their own device segment, so an out-of-range read faults.  values: case_data."""
     import torch
     from oracle import oracle as O
     from ragroute_amd.flat_index import FlatIndex
     from tests.test_guard_pages_gpu import _flush_to_end
-    from tests.util import int_data
-    rng = np.random.default_rng(c["seed"])
     d, n, nq, k = c["d"], c["n"], c["nq"], c["k"]
-    xb, xq = int_data(rng, n, d), int_data(rng, nq, d)
+    xb, xq, _ = case_data(c, n, values, c["metric"])
     idx = FlatIndex(d, metric=c["metric"], dtype=c["dtype"], device=dev)
     tdt = torch.float16 if c["dtype"] == "fp16" else torch.bfloat16
     xb_h = torch.zeros((n, idx.dim), dtype=tdt)
@@ -87,34 +117,40 @@ def segment_cases(seed, count, max_work=8e9):
     return out
 
 
-def run_segment_case(c, dev):
+def run_segment_case(c, dev, values="small", metric="ip"):
     """One segmented case on integer data against the oracle chain (per-source oracle top-k -> concat -> oracle merge), the matrix
-    flush against the end of its device segment, gaps poisoned."""
+    flush against the end of its device segment, gaps poisoned.  values: case_data; metric "l2": rr_flat_search_segments_l2 against
+    the ascending chain, the norm array flush against the end of its own mapping too, its gap entries NaN / +-inf."""
     import torch
     from ragroute_amd.flat_index import SegmentedIndex
     from tests.test_guard_pages_gpu import _flush_to_end
     from tests.test_segments_gpu import oracle_chain
-    from tests.util import int_data
-    rng = np.random.default_rng(c["seed"])
+    from tests.test_segments_l2_gpu import oracle_chain_l2
     d, rows, nq, k = c["d"], c["rows"], c["nq"], c["k"]
-    parts = [int_data(rng, n, d) for n in rows]
-    xq = int_data(rng, nq, d)
+    whole, xq, rng = case_data(c, rows, values, metric)
+    parts = np.split(whole, np.cumsum(rows)[:-1])
     mask = rng.random((nq, len(rows))) < c["density"]
-    seg = SegmentedIndex(d, rows, dtype=c["dtype"], device=dev)
+    seg = SegmentedIndex(d, rows, metric=metric, dtype=c["dtype"], device=dev)
     tdt = torch.float16 if c["dtype"] == "fp16" else torch.bfloat16
     host = torch.full((max(1, seg.n_rows_total), seg.dim), float("nan"), dtype=tdt)
     host[::5] = 30000.0
+    norms = torch.full((max(1, seg.n_rows_total),), float("nan"))
+    norms[::3], norms[1::3] = float("-inf"), float("inf")
     for s_, p in enumerate(parts):
         host[seg.begins[s_]: seg.begins[s_] + rows[s_]] = 0
         host[seg.begins[s_]: seg.begins[s_] + rows[s_], :d] = torch.from_numpy(p).to(tdt)
+        norms[seg.begins[s_]: seg.begins[s_] + rows[s_]] = torch.from_numpy(0.5 * (p.astype(np.float64) ** 2).sum(1)).float()
     keep_b, arena = _flush_to_end(host, dev)
     seg._xb = arena
+    keep_n = None
+    if metric == "l2":
+        keep_n, seg._hn = _flush_to_end(norms, dev)
     xq_h = torch.zeros((nq, seg.dim), dtype=tdt)
     xq_h[:, :d] = torch.from_numpy(xq).to(tdt)
     keep_q, xq_dev = _flush_to_end(xq_h, dev)
     D, I = seg.search_prepared(xq_dev, k, route_mask=torch.from_numpy(mask.astype(np.uint8)).to(dev))
     torch.cuda.synchronize()
-    Dr, Ir = oracle_chain(parts, xq, k, mask)
+    Dr, Ir = (oracle_chain_l2 if metric == "l2" else oracle_chain)(parts, xq, k, mask)
     ok = np.array_equal(I.cpu().numpy(), Ir) and np.array_equal(D.cpu().numpy(), Dr)
-    del keep_b, keep_q
+    del keep_b, keep_q, keep_n
     return ok

@@ -90,14 +90,21 @@ def test_bit_equal_to_oracle_on_raw_f32(gpu, metric, dtype, d, nq, k, n, list_le
     _equal(D, I, *_oracle(xb, xq, k, metric))
 
 
-@pytest.mark.parametrize("d,nq", [(768, 64), (768, 256), (2048, 16), (2048, 200), (4096, 200), (384, 5)])
-def test_eps_bounds_the_half_precision_scan(gpu, d, nq):
+@pytest.mark.parametrize("d,nq,scale", [(768, 64, 1), (768, 256, 1), (2048, 16, 1), (2048, 200, 1), (4096, 200, 1), (384, 5, 1),
+                                        (768, 64, 2.0 ** -18), (2048, 200, 2.0 ** -18)],
+                         ids=["768-64", "768-256", "2048-16", "2048-200", "4096-200", "384-5", "768-64-subnormal", "2048-200-subnormal"])
+def test_eps_bounds_the_half_precision_scan(gpu, d, nq, scale):
     """Every score the plain fp16 search returns is within eps(q) of the true (f64) dot product of the f32 inputs: the bound
-    gamma(dim) is not too small for the kernel family that serves this (dim, nq)."""
+    gamma(dim) is not too small for the kernel family that serves this (dim, nq).  scale 2^-18: rows 3 g 2^-18 (g gaussian), whose
+    half copies are mostly fp16 SUBNORMALS (|v| < 2^-14 for |g| < 5.3) - the proof assumes the matrix cores take subnormal fp16
+    inputs as they are, and eps(q) has no term for a flushed operand."""
     from ragroute_amd.flat_index import FlatIndex
     rng = np.random.default_rng(d * nq)
     n, k = 30_000, 32
-    xb, xq = _gauss(rng, n, d) * 3, _gauss(rng, nq, d)
+    xb, xq = _gauss(rng, n, d) * np.float32(3 * scale), _gauss(rng, nq, d)
+    if scale != 1:
+        stored = np.abs(half_round(xb[:256]))
+        assert np.mean((stored < 2.0 ** -14) & (stored > 0)) > 0.9, "the half copies should be mostly subnormal and nonzero"
     plain = FlatIndex(d, device=gpu)
     plain.add(xb)
     Dp, Ip = plain.search(xq, k)

@@ -18,7 +18,7 @@
 #   workload              bench.py --workload feb4rag|medrag at N=1, two ranks on the one device (gloo), sliced and whole placement;
 #                         tools/config34.py --plan 8 --with-one for both federations
 #   service [ROWS WINDOWS...]   tools/service_bench.py
-#   fuzz SEED COUNT [segments|big]   tools/fuzz_parity.py
+#   fuzz SEED COUNT [segments|big] [wide] [l2]   tools/fuzz_parity.py
 #   probe CYCLES          tools/remap_probe.py (stale-input root-cause probe)
 #   config2               config 2: bootstrap sample size A/B (development library) + per-search kernel timeline (tools/trace_gaps.py;
 #                         profiles/r04/config2_floor.json)
