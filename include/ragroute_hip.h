@@ -190,7 +190,7 @@ int rr_flat_search_screened(const void* d_xb, int dtype, const void* d_x8, const
  * half bytes).  A search scans the half copy for the list_len best rows per query, re-scores them from the f32 rows and checks a
  * rigorous bound on the half-precision scan's error (DESIGN.md "f32-faithful mode"): d_exact[q] = 1 means the k rows returned
  * for q are proven; 0 means the caller must repeat q (a longer list, then rr_flat_search_f32_exact).  Inner product / cosine
- * only (for cosine, pass rows and queries normalised by rr_l2_normalize_f32).  n_rows_total < 2^32 - 32.
+ * here, squared L2 further down (for cosine, pass rows and queries normalised by rr_l2_normalize_f32).  n_rows_total < 2^32 - 32.
  *   rr_faithful_build   d_stats f32[4] (error and norm maxima) from the f32 rows d_xf32 [n_rows][ld_f32] (d values used) and
  *                       their half copy d_xb [n_rows][dim]; rebuild after the corpus changes
  *   rr_flat_search_faithful  arguments of rr_flat_search_segments (a plain index is one segment), plus d_xf32 / ld_f32 / d (row
@@ -200,7 +200,34 @@ int rr_flat_search_screened(const void* d_xb, int dtype, const void* d_x8, const
  *   rr_flat_search_f32_exact  the exact f32 brute-force scan (the proof's last resort): queries qidx[0 .. n_idx) of d_xq_f32
  *                       [nq][d] (qidx device i32, NULL = queries 0 .. n_idx), each written to its own row of d_D / d_I [nq][k];
  *                       same segments, route mask and results as rr_flat_search_faithful; workspace
- *                       rr_flat_search_f32_exact_workspace_bytes(k, d) bytes.  Any k <= 1024, any row count, d <= 8192. */
+ *                       rr_flat_search_f32_exact_workspace_bytes(k, d) bytes.  Any k <= 1024, any row count, d <= 8192.
+ *
+ * Squared-L2 metric (the reference's wikipedia federation: L2 index files, lowest scores kept, ragroute/config.py:59-70,
+ * rerank.py:28-34), on unrounded and unnormalised f32 rows x and queries q.
+ * Definition.  D(q, x) is the f32 rounding of acc_d, acc_0 = 0, acc_{j+1} = fma(t_j, t_j, acc_j) with t_j = (double)q_j -
+ * (double)x_j, j ascending, all in f64 (the fma is part of the definition: t_j^2 is not exact in f64).  Rows by D ascending,
+ * ties by ascending matrix row; a zero distance is +0.0; a row or query holding a NaN gives a NaN distance and is never
+ * returned; a row whose distance rounds to +inf is a real row, listed behind the finite ones as (+inf, id); padding (+inf, -1).
+ * Segments, route mask and id offsets as rr_flat_search_faithful.
+ * Proof.  With a = q~, b = x~ the half copies, the L2 scan ranks by s~ = fl(fl(a.b) - h(b)), h = fl(|b|^2 / 2) of
+ * rr_half_sqnorms, and reports D~ = fl(qn - 2 s~), qn = fl(|a|^2); exactly, |a - b|^2 = |a|^2 - 2 (a.b - |b|^2 / 2).  A row
+ * outside a list of length L has s~ <= s~_L, hence |a - b|^2 >= D~_L - A(q) and
+ *     |q - x| >= |a - b| - |q - a| - |x - b| >= sqrt(max(0, D~_L - A(q))) - R(q),      R(q) = |q - q~| + Dmax,
+ *     A(q) = gamma(dim) (2 |a| X~max + X~max^2 + |a|^2) + 4 * 2^-23 (|a| + X~max)^2 + the bf16 flush-to-zero term
+ * (dot product, row norm, query norm; the single roundings of the scan's subtraction and of the final fl(qn - 2 s~); Dmax and
+ * X~max are words [0] and [2] of rr_faithful_build's d_stats, which serve both metrics; derivation in DESIGN.md "f32-faithful
+ * mode").  d_exact[q] = 1 when A and R are finite and either the list's last entry is padding (it holds every routed row) or
+ * sqrt(max(0, D~_L - A)) > R and (sqrt(max(0, D~_L - A)) - R)^2, rounded DOWN to f32, is STRICTLY greater than the k-th
+ * re-scored distance, so that no outside row can even tie it.  A is +inf where |a| X~max, X~max^2 or |a|^2 nears f32's range
+ * and NaN where an input is not finite; neither certifies.
+ * Ladder.  As for the inner product: the caller repeats an uncertified query with a longer list (up to 1024), then answers it
+ * with rr_flat_search_f32_exact_l2, the brute-force scan under the definition above.
+ *   rr_flat_search_faithful_l2  arguments of rr_flat_search_faithful plus d_half_sqnorm (rr_half_sqnorms of d_xb, aligned with
+ *                       it as in rr_flat_search_segments_l2; NULL with rows to scan is RR_ERR_INVALID); in place of d_eps,
+ *                       d_bound optional f32 [nq][2] = (A(q), R(q)), for tests; workspace
+ *                       rr_flat_search_faithful_l2_workspace_bytes(k, list_len, nq, dim) bytes (0 = invalid sizes)
+ *   rr_flat_search_f32_exact_l2  arguments, validation and workspace (rr_flat_search_f32_exact_workspace_bytes) of
+ *                       rr_flat_search_f32_exact */
 int rr_faithful_build(const float* d_xf32, int64_t ld_f32, const void* d_xb, int dtype, int64_t n_rows, int d, int dim, float* d_stats,
                       void* stream);
 size_t rr_flat_search_faithful_workspace_bytes(int k, int list_len, int nq, int dim);
@@ -212,6 +239,15 @@ size_t rr_flat_search_f32_exact_workspace_bytes(int k, int d);
 int rr_flat_search_f32_exact(const float* d_xf32, int64_t ld_f32, int64_t n_rows_total, int d, const rr_segment* segs, int n_segs,
                              const float* d_xq_f32, int nq, const int32_t* d_qidx, int n_idx, int k, float* d_D, int64_t* d_I, void* d_ws,
                              size_t ws_bytes, const uint8_t* d_route_mask, int64_t mask_stride, void* stream);
+size_t rr_flat_search_faithful_l2_workspace_bytes(int k, int list_len, int nq, int dim);
+int rr_flat_search_faithful_l2(const void* d_xb, const float* d_half_sqnorm, int dtype, const float* d_xf32, int64_t ld_f32,
+                               const float* d_stats, int64_t n_rows_total, int d, int dim, const rr_segment* segs, int n_segs,
+                               const void* d_xq, const float* d_xq_f32, int nq, int k, int list_len, float* d_D, int64_t* d_I,
+                               uint8_t* d_exact, float* d_bound, void* d_ws, size_t ws_bytes, const uint8_t* d_route_mask,
+                               int64_t mask_stride, void* stream);
+int rr_flat_search_f32_exact_l2(const float* d_xf32, int64_t ld_f32, int64_t n_rows_total, int d, const rr_segment* segs, int n_segs,
+                                const float* d_xq_f32, int nq, const int32_t* d_qidx, int n_idx, int k, float* d_D, int64_t* d_I,
+                                void* d_ws, size_t ws_bytes, const uint8_t* d_route_mask, int64_t mask_stride, void* stream);
 
 /* Measurement aid (bench.py): between rr_profile_begin and rr_profile_end every launch of the scan
  * kernel made by rr_flat_search on the calling thread is bracketed by HIP events on the launch stream.

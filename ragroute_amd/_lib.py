@@ -19,7 +19,8 @@ EXPORTS = ("rr_version", "rr_last_error", "rr_device_cus", "rr_padded_dim", "rr_
            "rr_flat_search_screened_workspace_bytes", "rr_flat_search_screened", "rr_router_workspace_bytes", "rr_router_mlp_ws",
            "rr_build_flags", "rr_merge_topk_gathered", "rr_flat_scan_kernel_name", "rr_flat_search_segments", "rr_flat_search_workspace_bytes_for",
            "rr_faithful_build", "rr_flat_search_faithful_workspace_bytes", "rr_flat_search_faithful",
-           "rr_flat_search_f32_exact_workspace_bytes", "rr_flat_search_f32_exact", "rr_flat_search_segments_l2")
+           "rr_flat_search_f32_exact_workspace_bytes", "rr_flat_search_f32_exact", "rr_flat_search_segments_l2",
+           "rr_flat_search_faithful_l2_workspace_bytes", "rr_flat_search_faithful_l2", "rr_flat_search_f32_exact_l2")
 
 
 class RouterWeightsStruct(ctypes.Structure):
@@ -96,6 +97,11 @@ def lib():
         L.rr_flat_search_f32_exact_workspace_bytes.restype = sz
         L.rr_flat_search_f32_exact.argtypes = [vp, i64, i64, i32, ctypes.POINTER(SegmentStruct), i32, vp, i32, vp, i32, i32, vp, vp, vp,
                                                sz, vp, i64, vp]
+        L.rr_flat_search_faithful_l2_workspace_bytes.argtypes = [i32, i32, i32, i32]
+        L.rr_flat_search_faithful_l2_workspace_bytes.restype = sz
+        L.rr_flat_search_faithful_l2.argtypes = [vp, vp, i32, vp, i64, vp, i64, i32, i32, ctypes.POINTER(SegmentStruct), i32, vp, vp, i32,
+                                                 i32, i32, vp, vp, vp, vp, vp, sz, vp, i64, vp]
+        L.rr_flat_search_f32_exact_l2.argtypes = L.rr_flat_search_f32_exact.argtypes
         L.rr_profile_begin.argtypes = [i32]
         L.rr_profile_end.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
         _LIB = L

@@ -310,7 +310,7 @@ const char kBuildFlags[] = "unknown (not built by ragroute_amd/_build.py)";
 
 extern "C" {
 
-int rr_version(void) { return 700; }  // 0.7.0: segmented squared-L2 search (rr_flat_search_segments_l2); 0.6.0: f32-faithful exact search (rr_flat_search_faithful, rr_flat_search_f32_exact); 0.5.0: row-split wide-row kernel for L2 / any k / 193+ queries (8 candidate buffers per workgroup on wide rows at every k: larger workspace), tuning variables ignored by product builds, cursor-free plain scans
+int rr_version(void) { return 800; }  // 0.8.0: f32-faithful exact search under the squared-L2 metric (rr_flat_search_faithful_l2, rr_flat_search_f32_exact_l2); 0.7.0: segmented squared-L2 search (rr_flat_search_segments_l2); 0.6.0: f32-faithful exact search (rr_flat_search_faithful, rr_flat_search_f32_exact); 0.5.0: row-split wide-row kernel for L2 / any k / 193+ queries (8 candidate buffers per workgroup on wide rows at every k: larger workspace), tuning variables ignored by product builds, cursor-free plain scans
 const char* rr_build_flags(void) { return kBuildFlags; }
 const char* rr_last_error(void) { return g_err; }
 int rr_device_cus(void) {
@@ -452,10 +452,10 @@ int rr_faithful_build(const float* xf32, int64_t ld_f32, const void* xb, int dty
 }
 
 struct FaithWs { float* eps; float* PL; int64_t* IL; char* inner; size_t inner_bytes, total; };
-static FaithWs carve_faithful(char* base, int list_len, int nq, int dim, int grid) {
+static FaithWs carve_faithful(char* base, int list_len, int nq, int dim, int grid, int eps_words = 1) {
   FaithWs w;
   Bump b{base};
-  w.eps = b.take<float>(nq);
+  w.eps = b.take<float>((size_t)nq * eps_words);
   w.PL = b.take<float>((size_t)nq * list_len);
   w.IL = b.take<int64_t>((size_t)nq * list_len);
   w.inner_bytes = carve(nullptr, list_len, grid, RR_DTYPE_F16, dim).total;
@@ -464,42 +464,70 @@ static FaithWs carve_faithful(char* base, int list_len, int nq, int dim, int gri
   return w;
 }
 
-size_t rr_flat_search_faithful_workspace_bytes(int k, int list_len, int nq, int dim) {
+static size_t faithful_workspace_bytes(int k, int list_len, int nq, int dim, int eps_words) {
   if (k < 1 || list_len < k || list_len > rr::kMaxK || nq < 0 || rr::scan_padded_dim(dim) != dim) return 0;
   const int grid = device_cus();
-  return grid > 0 ? carve_faithful(nullptr, list_len, nq, dim, grid).total : 0;
+  return grid > 0 ? carve_faithful(nullptr, list_len, nq, dim, grid, eps_words).total : 0;
+}
+size_t rr_flat_search_faithful_workspace_bytes(int k, int list_len, int nq, int dim) { return faithful_workspace_bytes(k, list_len, nq, dim, 1); }
+size_t rr_flat_search_faithful_l2_workspace_bytes(int k, int list_len, int nq, int dim) { return faithful_workspace_bytes(k, list_len, nq, dim, 2); }
+
+// Both metrics of the faithful search (`who` names the entry point in the messages).  l2: half_sqnorm is aligned with xb and
+// bound receives (A(q), R(q)) [nq][2]; otherwise bound is eps [nq].
+static int faithful_search(const char* who, bool l2, const void* xb, const float* half_sqnorm, int dtype, const float* xf32, int64_t ld_f32,
+                           const float* stats, int64_t n_rows_total, int d, int dim, const rr_segment* segs, int n_segs, const void* xq,
+                           const float* xq_f32, int nq, int k, int list_len, float* D, int64_t* I, uint8_t* exact, float* bound, void* ws,
+                           size_t ws_bytes, const uint8_t* route_mask, int64_t mask_stride, void* stream) {
+  using namespace rr;
+  hipStream_t st = (hipStream_t)stream;
+  if (!half_dtype(dtype)) return fail(RR_ERR_INVALID, "%s: bad dtype", who);
+  if (k < 1 || list_len < k || list_len > kMaxK) return fail(RR_ERR_INVALID, "%s: need 1 <= k <= list_len <= 1024", who);
+  if (scan_padded_dim(dim) != dim) return fail(RR_ERR_UNSUPPORTED, "%s: dim must equal rr_padded_dim(d)", who);
+  if (d < 1 || d > dim || ld_f32 < d || nq < 0) return fail(RR_ERR_INVALID, "%s: bad sizes", who);
+  SegHost h;
+  int64_t scanned = 0;
+  if (int rc = seg_host_from(segs, n_segs, n_rows_total, route_mask, mask_stride, who, h, scanned)) return rc;
+  if (nq == 0) return RR_OK;
+  if (!xq || !xq_f32 || !D || !I || !exact || !ws || !stats || ((!xb || !xf32) && scanned > 0)) return fail(RR_ERR_INVALID, "%s: null pointer", who);
+  if (l2 && !half_sqnorm && scanned > 0) return fail(RR_ERR_INVALID, "%s: null half_sqnorm", who);
+  const int grid = device_cus();
+  if (grid <= 0) return fail(RR_ERR_HIP, "%s: no HIP device", who);
+  FaithWs w = carve_faithful((char*)ws, list_len, nq, dim, grid, l2 ? 2 : 1);
+  if (ws_bytes < w.total)
+    return fail(RR_ERR_WORKSPACE, l2 ? "rr_flat_search_faithful_l2: workspace smaller than rr_flat_search_faithful_l2_workspace_bytes%s"
+                                     : "rr_flat_search_faithful: workspace smaller than rr_flat_search_faithful_workspace_bytes%s");
+  char where[96];
+  float* e_out = bound ? bound : w.eps;
+  snprintf(where, sizeof(where), "%s/queries", who);
+  if (int rc = hip_status(l2 ? launch_faithful_queries_l2(xq_f32, xq, dtype, nq, d, dim, (const uint32_t*)stats, e_out, st)
+                             : launch_faithful_queries(xq_f32, xq, dtype, nq, d, dim, (const uint32_t*)stats, e_out, st), where)) return rc;
+  // the half rows through the ordinary segmented scan at k' = list_len, listing MATRIX rows (id_offset := row_begin)
+  const FaithSegs fs = faith_segs(h);
+  for (uint32_t s = 0; s < h.n; ++s) h.id_offset[s] = h.row_begin[s];
+  // (a federation without rows has no norms to pass; any non-null marker selects the L2 finalize, never dereferenced)
+  static const float kEmpty = 0.f;
+  const float* hn = l2 ? (half_sqnorm ? half_sqnorm : &kEmpty) : nullptr;
+  if (int rc = flat_search_impl(xb, dtype, scanned, dim, xq, nq, list_len, w.PL, w.IL, 0, w.inner, w.inner_bytes, route_mask, mask_stride,
+                                hn, stream, &h)) return rc;
+  snprintf(where, sizeof(where), "%s/rescore", who);
+  return hip_status(launch_faithful_rescore(l2, xf32, ld_f32, d, xq_f32, nq, list_len, w.PL, w.IL, e_out, k, fs, route_mask, mask_stride, D, I,
+                                            exact, st), where);
 }
 
 int rr_flat_search_faithful(const void* xb, int dtype, const float* xf32, int64_t ld_f32, const float* stats, int64_t n_rows_total,
                             int d, int dim, const rr_segment* segs, int n_segs, const void* xq, const float* xq_f32, int nq, int k,
                             int list_len, float* D, int64_t* I, uint8_t* exact, float* eps, void* ws, size_t ws_bytes,
                             const uint8_t* route_mask, int64_t mask_stride, void* stream) {
-  using namespace rr;
-  hipStream_t st = (hipStream_t)stream;
-  if (!half_dtype(dtype)) return fail(RR_ERR_INVALID, "rr_flat_search_faithful: bad dtype%s");
-  if (k < 1 || list_len < k || list_len > kMaxK) return fail(RR_ERR_INVALID, "rr_flat_search_faithful: need 1 <= k <= list_len <= 1024%s");
-  if (scan_padded_dim(dim) != dim) return fail(RR_ERR_UNSUPPORTED, "rr_flat_search_faithful: dim must equal rr_padded_dim(d)%s");
-  if (d < 1 || d > dim || ld_f32 < d || nq < 0) return fail(RR_ERR_INVALID, "rr_flat_search_faithful: bad sizes%s");
-  SegHost h;
-  int64_t scanned = 0;
-  if (int rc = seg_host_from(segs, n_segs, n_rows_total, route_mask, mask_stride, "rr_flat_search_faithful", h, scanned)) return rc;
-  if (nq == 0) return RR_OK;
-  if (!xq || !xq_f32 || !D || !I || !exact || !ws || !stats || ((!xb || !xf32) && scanned > 0))
-    return fail(RR_ERR_INVALID, "rr_flat_search_faithful: null pointer%s");
-  const int grid = device_cus();
-  if (grid <= 0) return fail(RR_ERR_HIP, "rr_flat_search_faithful: no HIP device%s");
-  FaithWs w = carve_faithful((char*)ws, list_len, nq, dim, grid);
-  if (ws_bytes < w.total) return fail(RR_ERR_WORKSPACE, "rr_flat_search_faithful: workspace smaller than rr_flat_search_faithful_workspace_bytes%s");
-  float* e_out = eps ? eps : w.eps;
-  if (int rc = hip_status(launch_faithful_queries(xq_f32, xq, dtype, nq, d, dim, (const uint32_t*)stats, e_out, st),
-                          "rr_flat_search_faithful/queries")) return rc;
-  // the half rows through the ordinary segmented scan at k' = list_len, listing MATRIX rows (id_offset := row_begin)
-  const FaithSegs fs = faith_segs(h);
-  for (uint32_t s = 0; s < h.n; ++s) h.id_offset[s] = h.row_begin[s];
-  if (int rc = flat_search_impl(xb, dtype, scanned, dim, xq, nq, list_len, w.PL, w.IL, 0, w.inner, w.inner_bytes, route_mask, mask_stride,
-                                nullptr, stream, &h)) return rc;
-  return hip_status(launch_faithful_rescore(xf32, ld_f32, d, xq_f32, nq, list_len, w.PL, w.IL, e_out, k, fs, route_mask, mask_stride, D, I, exact, st),
-                    "rr_flat_search_faithful/rescore");
+  return faithful_search("rr_flat_search_faithful", false, xb, nullptr, dtype, xf32, ld_f32, stats, n_rows_total, d, dim, segs, n_segs, xq, xq_f32,
+                         nq, k, list_len, D, I, exact, eps, ws, ws_bytes, route_mask, mask_stride, stream);
+}
+
+int rr_flat_search_faithful_l2(const void* xb, const float* half_sqnorm, int dtype, const float* xf32, int64_t ld_f32, const float* stats,
+                               int64_t n_rows_total, int d, int dim, const rr_segment* segs, int n_segs, const void* xq, const float* xq_f32,
+                               int nq, int k, int list_len, float* D, int64_t* I, uint8_t* exact, float* bound, void* ws, size_t ws_bytes,
+                               const uint8_t* route_mask, int64_t mask_stride, void* stream) {
+  return faithful_search("rr_flat_search_faithful_l2", true, xb, half_sqnorm, dtype, xf32, ld_f32, stats, n_rows_total, d, dim, segs, n_segs, xq,
+                         xq_f32, nq, k, list_len, D, I, exact, bound, ws, ws_bytes, route_mask, mask_stride, stream);
 }
 
 // exact scan: per block of queries [G][k] lists -> (two-level if G*k > 8192) merge -> [k] -> D / I rows
@@ -521,43 +549,58 @@ size_t rr_flat_search_f32_exact_workspace_bytes(int k, int d) {
   return grid > 0 ? carve_exact(nullptr, rr::faithful_plan(k, d, grid, -1), k).total : 0;
 }
 
-int rr_flat_search_f32_exact(const float* xf32, int64_t ld_f32, int64_t n_rows_total, int d, const rr_segment* segs, int n_segs,
-                             const float* xq_f32, int nq, const int32_t* qidx, int n_idx, int k, float* D, int64_t* I, void* ws,
-                             size_t ws_bytes, const uint8_t* route_mask, int64_t mask_stride, void* stream) {
+// l2: rows are keyed by -D, so the descending merges below list the nearest first; the emit kernel turns the keys back into distances
+static int f32_exact_search(const char* who, bool l2, const float* xf32, int64_t ld_f32, int64_t n_rows_total, int d, const rr_segment* segs,
+                            int n_segs, const float* xq_f32, int nq, const int32_t* qidx, int n_idx, int k, float* D, int64_t* I, void* ws,
+                            size_t ws_bytes, const uint8_t* route_mask, int64_t mask_stride, void* stream) {
   using namespace rr;
   hipStream_t st = (hipStream_t)stream;
-  if (k < 1 || k > kMaxK) return fail(RR_ERR_INVALID, "rr_flat_search_f32_exact: k must be in [1, 1024]%s");
-  if (d < 1 || d > kMaxDim || ld_f32 < d || nq < 0 || n_idx < 0 || (!qidx && n_idx > nq))
-    return fail(RR_ERR_INVALID, "rr_flat_search_f32_exact: bad sizes%s");
+  if (k < 1 || k > kMaxK) return fail(RR_ERR_INVALID, "%s: k must be in [1, 1024]", who);
+  if (d < 1 || d > kMaxDim || ld_f32 < d || nq < 0 || n_idx < 0 || (!qidx && n_idx > nq)) return fail(RR_ERR_INVALID, "%s: bad sizes", who);
   SegHost h;
   int64_t scanned = 0;
-  if (int rc = seg_host_from(segs, n_segs, n_rows_total, route_mask, mask_stride, "rr_flat_search_f32_exact", h, scanned)) return rc;
+  if (int rc = seg_host_from(segs, n_segs, n_rows_total, route_mask, mask_stride, who, h, scanned)) return rc;
   if (n_idx == 0) return RR_OK;
-  if (!xq_f32 || !D || !I || !ws || (!xf32 && scanned > 0)) return fail(RR_ERR_INVALID, "rr_flat_search_f32_exact: null pointer%s");
+  if (!xq_f32 || !D || !I || !ws || (!xf32 && scanned > 0)) return fail(RR_ERR_INVALID, "%s: null pointer", who);
   const int grid = device_cus();
-  if (grid <= 0) return fail(RR_ERR_HIP, "rr_flat_search_f32_exact: no HIP device%s");
+  if (grid <= 0) return fail(RR_ERR_HIP, "%s: no HIP device", who);
   const FaithPlan p = faithful_plan(k, d, grid, scanned);
   ExactWs w = carve_exact((char*)ws, p, k);
-  if (ws_bytes < w.total) return fail(RR_ERR_WORKSPACE, "rr_flat_search_f32_exact: workspace smaller than rr_flat_search_f32_exact_workspace_bytes%s");
+  if (ws_bytes < w.total) return fail(RR_ERR_WORKSPACE, "%s: workspace smaller than rr_flat_search_f32_exact_workspace_bytes", who);
   const FaithSegs fs = faith_segs(h);
+  char where[96];
+  const auto at = [&](const char* step) { snprintf(where, sizeof(where), "%s/%s", who, step); return (const char*)where; };
   for (int q0 = 0; q0 < n_idx; q0 += p.nqb) {
     const int nqb = n_idx - q0 < p.nqb ? n_idx - q0 : p.nqb;
-    if (int rc = hip_status(launch_faithful_scan(p, xf32, ld_f32, d, scanned, xq_f32, qidx, q0, nqb, k, fs, route_mask, mask_stride, w.D1, w.I1, st),
-                            "rr_flat_search_f32_exact/scan")) return rc;
+    if (int rc = hip_status(launch_faithful_scan(l2, p, xf32, ld_f32, d, scanned, xq_f32, qidx, q0, nqb, k, fs, route_mask, mask_stride, w.D1, w.I1, st),
+                            at("scan"))) return rc;
     const float* Dm = w.D1;
     const int64_t* Im = w.I1;
     int lists = p.G;
     if (lists > p.gs) {   // level 1: groups of gs consecutive lists of one query -> [nqb][G / gs][k]
       const MergeSrc src{w.D1, w.I1, p.gs * k, 1, 0, 0, 0};
-      if (int rc = hip_status(launch_merge_topk(src, nqb * (lists / p.gs), p.gs * k, k, 1, w.D2, w.I2, st), "rr_flat_search_f32_exact/merge1"))
-        return rc;
+      if (int rc = hip_status(launch_merge_topk(src, nqb * (lists / p.gs), p.gs * k, k, 1, w.D2, w.I2, st), at("merge1"))) return rc;
       Dm = w.D2; Im = w.I2; lists /= p.gs;
     }
     const MergeSrc src{Dm, Im, lists * k, 1, 0, 0, 0};
-    if (int rc = hip_status(launch_merge_topk(src, nqb, lists * k, k, 1, w.D3, w.I3, st), "rr_flat_search_f32_exact/merge")) return rc;
-    if (int rc = hip_status(launch_faithful_emit(w.D3, w.I3, qidx, q0, nqb, k, fs, D, I, st), "rr_flat_search_f32_exact/emit")) return rc;
+    if (int rc = hip_status(launch_merge_topk(src, nqb, lists * k, k, 1, w.D3, w.I3, st), at("merge"))) return rc;
+    if (int rc = hip_status(launch_faithful_emit(l2, w.D3, w.I3, qidx, q0, nqb, k, fs, D, I, st), at("emit"))) return rc;
   }
   return RR_OK;
+}
+
+int rr_flat_search_f32_exact(const float* xf32, int64_t ld_f32, int64_t n_rows_total, int d, const rr_segment* segs, int n_segs,
+                             const float* xq_f32, int nq, const int32_t* qidx, int n_idx, int k, float* D, int64_t* I, void* ws,
+                             size_t ws_bytes, const uint8_t* route_mask, int64_t mask_stride, void* stream) {
+  return f32_exact_search("rr_flat_search_f32_exact", false, xf32, ld_f32, n_rows_total, d, segs, n_segs, xq_f32, nq, qidx, n_idx, k, D, I, ws,
+                          ws_bytes, route_mask, mask_stride, stream);
+}
+
+int rr_flat_search_f32_exact_l2(const float* xf32, int64_t ld_f32, int64_t n_rows_total, int d, const rr_segment* segs, int n_segs,
+                                const float* xq_f32, int nq, const int32_t* qidx, int n_idx, int k, float* D, int64_t* I, void* ws,
+                                size_t ws_bytes, const uint8_t* route_mask, int64_t mask_stride, void* stream) {
+  return f32_exact_search("rr_flat_search_f32_exact_l2", true, xf32, ld_f32, n_rows_total, d, segs, n_segs, xq_f32, nq, qidx, n_idx, k, D, I, ws,
+                          ws_bytes, route_mask, mask_stride, stream);
 }
 
 // ---- int8 screening copy ---------------------------------------------------------------------------------

@@ -15,6 +15,28 @@
 // checker the results are bit-compared with.  The
 // f32 x f32 products are exact in f64, so fma and multiply-then-add give the same sums.
 // No reference counterpart: the reference's faiss.IndexFlatIP scans every f32 row (data_source.py:158,186,203).
+//
+// Squared L2 (rr_flat_search_faithful_l2 / rr_flat_search_f32_exact_l2; the metric is a template argument of the re-score, scan
+// and emit kernels).  D(q, x) = f32 rounding of acc_d, acc_{j+1} = fma(t_j, t_j, acc_j), t_j = (double)q_j - (double)x_j, j
+// ascending: here the fma IS part of the definition (t_j is exact, t_j^2 is not).  Rows by D ascending, ties by ascending row,
+// zero as +0.0, NaN never returned, a distance that rounds to +inf is a real row behind the finite ones, padding (+inf, -1).
+// Rows are keyed by -D, so the descending sorts and merges list the nearest first.  The proof, with a = q~, b = x~:
+//     the L2 scan ranks by s~ = fl(fl(a.b) - h(b)), h = fl(|b|^2 / 2) (rr_half_sqnorms); in every kernel the norm is taken off
+//     the finished dot product by one f32 subtraction (the wide-row kernels ahead of the epilogue, the row-split kernel after
+//     its halves are summed), and finalize_kernel<.., L2> reports D~ = fl(qn - 2 s~), qn = fl(|a|^2);
+//     exactly |a - b|^2 = |a|^2 - 2 (a.b - |b|^2 / 2), and with X = X~max >= |b|, g = gamma(dim), u = one f32 rounding:
+//       |fl(a.b) - a.b| <= g |a| X,  |h - |b|^2/2| <= g X^2 / 2,  |qn - |a|^2| <= g |a|^2,
+//       the subtraction errs by <= u (|a| X + X^2/2)(1 + g), the finalize by <= u/(1-u) |D~|, |D~| <= (|a| + X)^2 (1 + g)(1 + u)
+//  => |a - b|^2 >= D~ - A(q),  A(q) = g (2 |a| X + X^2 + |a|^2) + 4 2^-23 (|a| + X)^2 + 4 dim 2^-120 (1 + |a| + X)
+//     (the u terms sum to < 2 u (|a| + X)^2 (1 + g)(1 + u) with u = 2^-24: A carries 8x that; the last term is the bf16
+//     flush-to-zero term of eps(q) for the dot product, both norms and a subnormal difference)
+// every row outside a list of length L has s~ <= s~_L, hence D~ >= D~_L (D~ is non-increasing in s~) and
+//     |q - x| >= |a - b| - |q - q~| - |x - x~| >= sqrt(max(0, D~_L - A(q))) - R(q),   R(q) = |q - q~| + Dmax
+// d_exact[q] = 1 when A and R are finite and the list's last entry is padding, or sqrt(max(0, D~_L - A)) > R and
+// (sqrt(max(0, D~_L - A)) - R)^2, rounded DOWN to f32, is STRICTLY greater than the k-th re-scored distance: f32 rounding is
+// monotone, so no outside row can reach or tie it.  A is +inf where |a| X, X^2 or |a|^2 nears f32's range, NaN where an input
+// is not finite; neither certifies.  Dmax and X~max are stats words [0] and [2]: faithful_stats_kernel serves both metrics.
+// (DESIGN.md "f32-faithful mode" has the derivation line by line.)
 #include "rr_common.h"
 #include "rr_kernels.h"
 #include "rr_sort.h"
@@ -40,11 +62,26 @@ __device__ __forceinline__ float up_f32(double v) {
   return f;
 }
 
+// largest f32 <= v (NaN stays NaN)
+__device__ __forceinline__ float down_f32(double v) {
+  float f = (float)v;
+  if ((double)f > v) {
+    const uint32_t b = __float_as_uint(f);
+    if ((b & 0x7FFFFFFFu) == 0) f = __uint_as_float(0x80000001u);
+    else f = __uint_as_float((b & 0x80000000u) ? b + 1 : b - 1);
+  }
+  return f;
+}
+
 // order key of a re-scored row: -0 and +0 are one score (scores compare with ==), NaN scores are never returned
 __device__ __forceinline__ uint64_t score_key(float s, uint32_t row) {
   if (s != s) return 0ull;
   return make_key(s == 0.f ? 0.f : s, row);
 }
+
+// L2: a row is keyed by -D, so that the descending sorts and merges of this file list the nearest row first and equal distances
+// by ascending row; the distance comes back out of a key's score as +0.0 for zero (never -0.0), +inf for a row that far away
+__device__ __forceinline__ float dist_of_score(float s) { return s == 0.f ? 0.f : -s; }
 
 __device__ __forceinline__ int seg_of(const FaithSegs& g, uint32_t row) {
   for (uint32_t s = 0; s < g.n; ++s)
@@ -68,6 +105,37 @@ __device__ __forceinline__ double dot_f64(const float* __restrict__ x, const flo
     for (int j = 0; j < d; ++j) acc = fma((double)x[j], (double)q[j], acc);
   }
   return acc;
+}
+
+// f64 squared distance of one f32 row from an f32 query in LDS: acc = fma(t, t, acc), t = (double)q_j - (double)x_j (exact), j
+// ascending.  The fma is written out: t * t is NOT exact in f64, so multiply-then-add would round twice and give other sums.
+__device__ __forceinline__ double sqdist_f64(const float* __restrict__ x, const float* q, int d, bool vec4) {
+  double acc = 0.0;
+  if (vec4) {
+    const float4* x4 = (const float4*)x;
+    for (int j = 0; j < d / 4; ++j) {
+      const float4 v = x4[j];
+      const double t0 = (double)q[4 * j] - (double)v.x, t1 = (double)q[4 * j + 1] - (double)v.y;
+      const double t2 = (double)q[4 * j + 2] - (double)v.z, t3 = (double)q[4 * j + 3] - (double)v.w;
+      acc = fma(t0, t0, acc);
+      acc = fma(t1, t1, acc);
+      acc = fma(t2, t2, acc);
+      acc = fma(t3, t3, acc);
+    }
+  } else {
+    for (int j = 0; j < d; ++j) {
+      const double t = (double)q[j] - (double)x[j];
+      acc = fma(t, t, acc);
+    }
+  }
+  return acc;
+}
+
+// the f32 score one (row, query) pair is ordered by: q.x, or -D(q, x) under the L2 metric
+template <bool L2>
+__device__ __forceinline__ float pair_score(const float* __restrict__ x, const float* q, int d, bool vec4) {
+  if constexpr (L2) return -(float)sqdist_f64(x, q, d, vec4);
+  else return (float)dot_f64(x, q, d, vec4);
 }
 
 // stats words (f32 bit patterns of non-negative values, so that an unsigned max is a float max; NaN sorts above +inf):
@@ -103,6 +171,19 @@ __global__ __launch_bounds__(256) void faithful_stats_kernel(const float* __rest
   }
 }
 
+// one wave: e2 = |q - q~|^2 and h2 = |q~|^2 of one query and its half copy (f64, in every lane)
+template <typename T>
+__device__ __forceinline__ void query_norms(const float* __restrict__ xq, const T* __restrict__ xqh, int d, int lane, double& e2, double& h2) {
+  e2 = h2 = 0.0;
+  for (int j = lane; j < d; j += 64) {
+    const double x = (double)xq[j], h = (double)(float)xqh[j];
+    e2 = fma(x - h, x - h, e2);
+    h2 = fma(h, h, h2);
+  }
+  e2 = wsum_d(e2);
+  h2 = wsum_d(h2);
+}
+
 // one wave per query: eps(q) (module header), rounded up; +inf where the scan could overflow (|q~| X~max near FLT_MAX), NaN
 // where an input is not finite — neither ever proves a list
 template <typename T>
@@ -111,14 +192,8 @@ __global__ __launch_bounds__(256) void faithful_queries_kernel(const float* __re
   const int lane = threadIdx.x & 63;
   const int q = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (q >= nq) return;
-  double e2 = 0.0, h2 = 0.0;
-  for (int j = lane; j < d; j += 64) {
-    const double x = (double)xq[(size_t)q * d + j], h = (double)(float)xqh[(size_t)q * dim + j];
-    e2 = fma(x - h, x - h, e2);
-    h2 = fma(h, h, h2);
-  }
-  e2 = wsum_d(e2);
-  h2 = wsum_d(h2);
+  double e2, h2;
+  query_norms(xq + (size_t)q * d, xqh + (size_t)q * dim, d, lane, e2, h2);
   if (lane == 0) {
     const double dmax = __uint_as_float(stats[0]), xmax = __uint_as_float(stats[1]), hmax = __uint_as_float(stats[2]);
     const double en = sqrt(e2), hn = sqrt(h2);
@@ -133,8 +208,33 @@ __global__ __launch_bounds__(256) void faithful_queries_kernel(const float* __re
   }
 }
 
+// one wave per query, L2 metric: bound[q] = (A(q), R(q)) of the module header, each rounded up.  A is +inf where |q~| X~max, X~max^2
+// or |q~|^2 nears f32's range (the scan's f32 arithmetic could overflow), NaN where an input is not finite — neither certifies
+template <typename T>
+__global__ __launch_bounds__(256) void faithful_queries_l2_kernel(const float* __restrict__ xq, const T* __restrict__ xqh, int nq, int d, int dim,
+                                                                  const uint32_t* __restrict__ stats, double gamma, float* __restrict__ bound) {
+  const int lane = threadIdx.x & 63;
+  const int q = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (q >= nq) return;
+  double e2, h2;
+  query_norms(xq + (size_t)q * d, xqh + (size_t)q * dim, d, lane, e2, h2);
+  if (lane == 0) {
+    const double dmax = __uint_as_float(stats[0]), hmax = __uint_as_float(stats[2]);
+    const double en = sqrt(e2), hn = sqrt(h2), u = 0x1p-23;
+    // gamma terms: dot product (x2), row norm, query norm; 4 u (|a| + X~max)^2: the two single roundings (u = 2^-23 where round to
+    // nearest gives 2^-24: 8x what the derivation needs); 1.0001: the f64 roundings of the norms above; last term: products that
+    // leave the f32 normal range (bf16 only, at most 2^-126 each, in the dot product and both norms) and subnormal differences
+    double a = 1.0001 * (gamma * (2.0 * hn * hmax + hmax * hmax + hn * hn) + 4.0 * u * (hn + hmax) * (hn + hmax)) +
+               4.0 * (double)dim * 0x1p-120 * (1.0 + hn + hmax);
+    if (hn * hmax > 1e37 || hmax * hmax > 1e37 || hn * hn > 1e37) a = __builtin_inf();
+    bound[2 * (size_t)q] = up_f32(a);
+    bound[2 * (size_t)q + 1] = up_f32(1.0001 * en + dmax);
+  }
+}
+
 // one workgroup per query: f32 scores of the listed rows (matrix rows, one thread per row), sort by (score, row), emit the
 // top k with ids mapped through the segment table, certify
+template <bool L2>
 __global__ __launch_bounds__(256) void faithful_rescore_kernel(const float* __restrict__ xf, int64_t ld, int d, const float* __restrict__ xq, int L,
                                                                const float* __restrict__ PL, const int64_t* __restrict__ IL,
                                                                const float* __restrict__ eps, int k, const FaithSegs segs,
@@ -154,7 +254,7 @@ __global__ __launch_bounds__(256) void faithful_rescore_kernel(const float* __re
     // outside it still scores <= the list's last)
     const int s = row >= 0 ? seg_of(segs, (uint32_t)row) : -1;
     const bool routed = s >= 0 && (segs.mask_col[s] < 0 || !mask || mask[(size_t)q * mask_stride + segs.mask_col[s]]);
-    keys[c] = routed ? score_key((float)dot_f64(xf + row * ld, qf, d, vec4), (uint32_t)row) : 0ull;
+    keys[c] = routed ? score_key(pair_score<L2>(xf + row * ld, qf, d, vec4), (uint32_t)row) : 0ull;
   }
   __syncthreads();
   bitonic_sort_desc(keys, np);
@@ -166,22 +266,34 @@ __global__ __launch_bounds__(256) void faithful_rescore_kernel(const float* __re
       const int s = seg_of(segs, row);
       id = s >= 0 ? segs.id_offset[s] + (int64_t)(row - segs.row_begin[s]) : -1;
     }
-    D[(size_t)q * k + i] = key ? key_score(key) : -__builtin_inff();
+    if constexpr (L2) D[(size_t)q * k + i] = key ? dist_of_score(key_score(key)) : __builtin_inff();
+    else D[(size_t)q * k + i] = key ? key_score(key) : -__builtin_inff();
     I[(size_t)q * k + i] = id;
   }
   if (threadIdx.x == 0) {
-    const float e = eps[q];
-    bool ok = false;
-    if (e - e == 0.f) {  // finite: no input overflowed the half type, no NaN
-      if (IL[(size_t)q * L + L - 1] < 0) {
-        ok = true;  // the list holds every row the scan ranked: the whole (routed) corpus
-      } else {
-        const float sL = PL[(size_t)q * L + L - 1];
-        const uint64_t kth = keys[k - 1];
-        ok = kth != 0 && sL - sL == 0.f && up_f32((double)sL + (double)e) < key_score(kth);
+    // `finite`: no input overflowed the half type, no NaN - every row the scan could rank is in its order.  `beats`: the bound on
+    // every row outside the list, rounded towards the k-th re-scored row, stays strictly on its far side
+    const float tail = PL[(size_t)q * L + L - 1];
+    const uint64_t kth = keys[k - 1];
+    const bool have = kth != 0 && tail - tail == 0.f;
+    bool finite, beats = false;
+    if constexpr (L2) {  // eps = bound [nq][2] = (A, R); tail = D~_L, the largest distance the half-precision search reports
+      const float A = eps[2 * (size_t)q], R = eps[2 * (size_t)q + 1];
+      finite = A - A == 0.f && R - R == 0.f;
+      if (have) {
+        // every row outside the list: |q - x| >= sqrt(max(0, D~_L - A)) - R.  (1 - 2^-40) twice: the f64 roundings of the
+        // difference, the root and the square, and the relative error d 2^-53 of the f64 chain that such a row's own D sums
+        const double m = (double)tail - (double)A;
+        const double r = sqrt(m > 0.0 ? m : 0.0) * (1.0 - 0x1p-40) - (double)R;
+        beats = r > 0.0 && down_f32(r * r * (1.0 - 0x1p-40)) > dist_of_score(key_score(kth));
       }
+    } else {
+      const float e = eps[q];
+      finite = e - e == 0.f;
+      beats = have && up_f32((double)tail + (double)e) < key_score(kth);
     }
-    exact[q] = ok ? 1 : 0;
+    // a list whose last entry is padding holds every row the scan ranked: the whole (routed) corpus
+    exact[q] = finite && (IL[(size_t)q * L + L - 1] < 0 || beats) ? 1 : 0;
   }
 }
 
@@ -190,6 +302,7 @@ __global__ __launch_bounds__(256) void faithful_rescore_kernel(const float* __re
 // its k best keys sorted in keys[0, k) and collects the keys of a 256-row tile that beat the current k-th in keys[k, k + 256);
 // a tile that produced any is merged by one bitonic sort.  Output [nqb][G][k] (score, matrix row), padding (-inf, -1).
 constexpr int kScanQueries = 16;
+template <bool L2>
 __global__ __launch_bounds__(256) void faithful_scan_kernel(const float* __restrict__ xf, int64_t ld, int d, int64_t n_rows,
                                                             const float* __restrict__ xq, const int32_t* __restrict__ qidx, int q0, int nqb,
                                                             int k, int P, int64_t rpw, const FaithSegs segs, const uint8_t* __restrict__ mask,
@@ -233,10 +346,19 @@ __global__ __launch_bounds__(256) void faithful_scan_kernel(const float* __restr
           for (int b = 0; b < kScanQueries; ++b) {
             if (b < nqb) {
               const float* qb = qs + (size_t)b * d + 4 * j;
-              acc[b] = fma((double)v.x, (double)qb[0], acc[b]);
-              acc[b] = fma((double)v.y, (double)qb[1], acc[b]);
-              acc[b] = fma((double)v.z, (double)qb[2], acc[b]);
-              acc[b] = fma((double)v.w, (double)qb[3], acc[b]);
+              if constexpr (L2) {
+                const double t0 = (double)qb[0] - (double)v.x, t1 = (double)qb[1] - (double)v.y;
+                const double t2 = (double)qb[2] - (double)v.z, t3 = (double)qb[3] - (double)v.w;
+                acc[b] = fma(t0, t0, acc[b]);
+                acc[b] = fma(t1, t1, acc[b]);
+                acc[b] = fma(t2, t2, acc[b]);
+                acc[b] = fma(t3, t3, acc[b]);
+              } else {
+                acc[b] = fma((double)v.x, (double)qb[0], acc[b]);
+                acc[b] = fma((double)v.y, (double)qb[1], acc[b]);
+                acc[b] = fma((double)v.z, (double)qb[2], acc[b]);
+                acc[b] = fma((double)v.w, (double)qb[3], acc[b]);
+              }
             }
           }
         }
@@ -244,14 +366,22 @@ __global__ __launch_bounds__(256) void faithful_scan_kernel(const float* __restr
         for (int j = 0; j < d; ++j) {
           const double v = (double)x[j];
 #pragma unroll
-          for (int b = 0; b < kScanQueries; ++b)
-            if (b < nqb) acc[b] = fma(v, (double)qs[(size_t)b * d + j], acc[b]);
+          for (int b = 0; b < kScanQueries; ++b) {
+            if (b < nqb) {
+              if constexpr (L2) {
+                const double t = (double)qs[(size_t)b * d + j] - v;
+                acc[b] = fma(t, t, acc[b]);
+              } else {
+                acc[b] = fma(v, (double)qs[(size_t)b * d + j], acc[b]);
+              }
+            }
+          }
         }
       }
 #pragma unroll
       for (int b = 0; b < kScanQueries; ++b) {
         if (b < nqb && ((sel[b] >> s) & 1u)) {
-          const uint64_t key = score_key((float)acc[b], (uint32_t)row);
+          const uint64_t key = score_key(L2 ? -(float)acc[b] : (float)acc[b], (uint32_t)row);
           if (key > thr[b]) {
             const uint32_t slot = atomicAdd(&cnt[b], 1u);  // < 256: one candidate per thread and tile
             keys[(size_t)b * P + k + slot] = key;
@@ -286,6 +416,7 @@ __global__ __launch_bounds__(256) void faithful_scan_kernel(const float* __restr
 }
 
 // block b of the fallback: (score, matrix row) [nqb][k] -> the caller's D / I rows qidx[q0 + b], ids through the segment table
+template <bool L2>
 __global__ __launch_bounds__(256) void faithful_emit_kernel(const float* __restrict__ Din, const int64_t* __restrict__ Iin, const int32_t* __restrict__ qidx,
                                                             int q0, int k, const FaithSegs segs, float* __restrict__ D, int64_t* __restrict__ I) {
   const int b = blockIdx.x;
@@ -297,7 +428,8 @@ __global__ __launch_bounds__(256) void faithful_emit_kernel(const float* __restr
       const int s = seg_of(segs, (uint32_t)row);
       id = s >= 0 ? segs.id_offset[s] + (row - (int64_t)segs.row_begin[s]) : -1;
     }
-    D[qi * k + j] = id >= 0 ? Din[(size_t)b * k + j] : -__builtin_inff();
+    if constexpr (L2) D[qi * k + j] = id >= 0 ? dist_of_score(Din[(size_t)b * k + j]) : __builtin_inff();
+    else D[qi * k + j] = id >= 0 ? Din[(size_t)b * k + j] : -__builtin_inff();
     I[qi * k + j] = id;
   }
 }
@@ -366,28 +498,43 @@ hipError_t launch_faithful_queries(const float* xq, const void* xqh, int dtype, 
   return hipGetLastError();
 }
 
-hipError_t launch_faithful_rescore(const float* xf, int64_t ld, int d, const float* xq, int nq, int L, const float* PL, const int64_t* IL,
-                                   const float* eps, int k, const FaithSegs& segs, const uint8_t* mask, int64_t mask_stride, float* D,
-                                   int64_t* I, uint8_t* exact, hipStream_t st) {
+hipError_t launch_faithful_queries_l2(const float* xq, const void* xqh, int dtype, int nq, int d, int dim, const uint32_t* stats, float* bound,
+                                      hipStream_t st) {
   if (nq == 0) return hipSuccess;
-  hipLaunchKernelGGL(faithful_rescore_kernel, dim3(nq), dim3(256), 0, st, xf, ld, d, xq, L, PL, IL, eps, k, segs, mask, mask_stride, D, I,
-                     exact);
+  const int g = (nq + 3) / 4;
+  const double gamma = faithful_gamma(dim);
+  if (dtype == RR_DTYPE_F16)
+    hipLaunchKernelGGL(faithful_queries_l2_kernel<_Float16>, dim3(g), dim3(256), 0, st, xq, (const _Float16*)xqh, nq, d, dim, stats, gamma, bound);
+  else if (dtype == RR_DTYPE_BF16)
+    hipLaunchKernelGGL(faithful_queries_l2_kernel<__bf16>, dim3(g), dim3(256), 0, st, xq, (const __bf16*)xqh, nq, d, dim, stats, gamma, bound);
+  else
+    return hipErrorInvalidValue;
   return hipGetLastError();
 }
 
-hipError_t launch_faithful_scan(const FaithPlan& p, const float* xf, int64_t ld, int d, int64_t n_rows, const float* xq, const int32_t* qidx,
+hipError_t launch_faithful_rescore(bool l2, const float* xf, int64_t ld, int d, const float* xq, int nq, int L, const float* PL,
+                                   const int64_t* IL, const float* eps, int k, const FaithSegs& segs, const uint8_t* mask,
+                                   int64_t mask_stride, float* D, int64_t* I, uint8_t* exact, hipStream_t st) {
+  if (nq == 0) return hipSuccess;
+  hipLaunchKernelGGL(l2 ? faithful_rescore_kernel<true> : faithful_rescore_kernel<false>, dim3(nq), dim3(256), 0, st, xf, ld, d, xq, L, PL,
+                     IL, eps, k, segs, mask, mask_stride, D, I, exact);
+  return hipGetLastError();
+}
+
+hipError_t launch_faithful_scan(bool l2, const FaithPlan& p, const float* xf, int64_t ld, int d, int64_t n_rows, const float* xq, const int32_t* qidx,
                                 int q0, int nqb, int k, const FaithSegs& segs, const uint8_t* mask, int64_t mask_stride, float* outD,
                                 int64_t* outI, hipStream_t st) {
   int64_t rpw = (n_rows + p.G - 1) / p.G;
   rpw = (rpw + 255) / 256 * 256;
-  hipLaunchKernelGGL(faithful_scan_kernel, dim3(p.G), dim3(256), p.lds, st, xf, ld, d, n_rows, xq, qidx, q0, nqb, k, p.P, rpw, segs, mask,
-                     mask_stride, outD, outI);
+  hipLaunchKernelGGL(l2 ? faithful_scan_kernel<true> : faithful_scan_kernel<false>, dim3(p.G), dim3(256), p.lds, st, xf, ld, d, n_rows, xq,
+                     qidx, q0, nqb, k, p.P, rpw, segs, mask, mask_stride, outD, outI);
   return hipGetLastError();
 }
 
-hipError_t launch_faithful_emit(const float* Din, const int64_t* Iin, const int32_t* qidx, int q0, int nqb, int k, const FaithSegs& segs,
+hipError_t launch_faithful_emit(bool l2, const float* Din, const int64_t* Iin, const int32_t* qidx, int q0, int nqb, int k, const FaithSegs& segs,
                                 float* D, int64_t* I, hipStream_t st) {
-  hipLaunchKernelGGL(faithful_emit_kernel, dim3(nqb), dim3(256), 0, st, Din, Iin, qidx, q0, k, segs, D, I);
+  hipLaunchKernelGGL(l2 ? faithful_emit_kernel<true> : faithful_emit_kernel<false>, dim3(nqb), dim3(256), 0, st, Din, Iin, qidx, q0, k, segs,
+                     D, I);
   return hipGetLastError();
 }
 

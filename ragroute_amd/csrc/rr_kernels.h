@@ -136,13 +136,16 @@ hipError_t launch_faithful_build(const float* xf, int64_t ld, const void* xb, in
                                  hipStream_t st);
 hipError_t launch_faithful_queries(const float* xq, const void* xqh, int dtype, int nq, int d, int dim, const uint32_t* stats, float* eps,
                                    hipStream_t st);
-hipError_t launch_faithful_rescore(const float* xf, int64_t ld, int d, const float* xq, int nq, int L, const float* PL, const int64_t* IL,
-                                   const float* eps, int k, const FaithSegs& segs, const uint8_t* mask, int64_t mask_stride, float* D,
-                                   int64_t* I, uint8_t* exact, hipStream_t st);
-hipError_t launch_faithful_scan(const FaithPlan& p, const float* xf, int64_t ld, int d, int64_t n_rows, const float* xq, const int32_t* qidx,
+hipError_t launch_faithful_queries_l2(const float* xq, const void* xqh, int dtype, int nq, int d, int dim, const uint32_t* stats, float* bound,
+                                      hipStream_t st);   // bound [nq][2] = (A(q), R(q))
+// l2: the squared-L2 forms (rows keyed by -D; eps = the [nq][2] bound, PL = the half-precision search's distances)
+hipError_t launch_faithful_rescore(bool l2, const float* xf, int64_t ld, int d, const float* xq, int nq, int L, const float* PL,
+                                   const int64_t* IL, const float* eps, int k, const FaithSegs& segs, const uint8_t* mask,
+                                   int64_t mask_stride, float* D, int64_t* I, uint8_t* exact, hipStream_t st);
+hipError_t launch_faithful_scan(bool l2, const FaithPlan& p, const float* xf, int64_t ld, int d, int64_t n_rows, const float* xq, const int32_t* qidx,
                                 int q0, int nqb, int k, const FaithSegs& segs, const uint8_t* mask, int64_t mask_stride, float* outD,
                                 int64_t* outI, hipStream_t st);
-hipError_t launch_faithful_emit(const float* Din, const int64_t* Iin, const int32_t* qidx, int q0, int nqb, int k, const FaithSegs& segs,
+hipError_t launch_faithful_emit(bool l2, const float* Din, const int64_t* Iin, const int32_t* qidx, int q0, int nqb, int k, const FaithSegs& segs,
                                 float* D, int64_t* I, hipStream_t st);
 
 // router.hip

@@ -244,7 +244,7 @@ class DataSource:
         self._batcher = None
         self.batch_window_ms = float(os.environ.get("RAGROUTE_BATCH_WINDOW_MS", 0.2))
         # RAGROUTE_EXACT_F32=1: keep the index file's f32 rows beside the half copy and return the reference's f32 results
-        # (FlatIndex exact_f32; 3x the half bytes of HBM)
+        # (FlatIndex exact_f32, or exact_l2 where the index file's metric is L2; 3x the half bytes of HBM)
         self.exact_f32 = os.environ.get("RAGROUTE_EXACT_F32", "0") not in ("", "0")
 
     # -- loading (data_source.py:69-80) -------------------------------------------------------------
@@ -284,7 +284,7 @@ class DataSource:
             index = xb
         else:
             metric = getattr(self, "index_metric", "ip")
-            kw = {"exact_f32": True} if self.exact_f32 else {}
+            kw = {"exact_l2" if metric == "l2" else "exact_f32": True} if self.exact_f32 else {}
             index = FlatIndex(xb.shape[1], metric=metric, dtype=self.dtype, device=self.pick_device(), **kw)
             index.reserve(xb.shape[0])
             index.add(xb)

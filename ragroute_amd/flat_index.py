@@ -34,10 +34,15 @@ def _as_f32_rows(part, device):
 
 
 class _Faithful:
-    """The f32-faithful mode shared by FlatIndex and SegmentedIndex (exact_f32=True; C ABI rr_flat_search_faithful): the f32 rows
+    """The f32-faithful mode shared by FlatIndex and SegmentedIndex (exact_f32=True; C ABI rr_flat_search_faithful; under the
+    squared-L2 metric exact_l2=True and rr_flat_search_faithful_l2, which also reads the half squared norms `_hn`): the f32 rows
     `_xf` beside the half copy `_xb`, their error / norm maxima `_fstats`, and the search that proves every query's top-k on the
     f32 rows — a query whose proof fails is repeated with a list of 1024 rows (`faithful_retries` counts those queries), and
     what is still unproven is answered by the exact f32 scan (`faithful_fallbacks`)."""
+
+    @property
+    def _faith(self):
+        return self.exact_f32 or self.exact_l2
 
     def _faithful_init(self, n_rows):
         self._xf = torch.zeros((max(1, n_rows), self.d), dtype=torch.float32, device=self.device)
@@ -87,7 +92,8 @@ class _Faithful:
         key = (k, L, nq)
         ws = self._ws_faithful.get(key)
         if ws is None:
-            nbytes = lib().rr_flat_search_faithful_workspace_bytes(k, L, nq, self.dim)
+            query = lib().rr_flat_search_faithful_l2_workspace_bytes if self.exact_l2 else lib().rr_flat_search_faithful_workspace_bytes
+            nbytes = query(k, L, nq, self.dim)
             if nbytes == 0:
                 raise ValueError(f"need 1 <= k <= list_len <= {_lib.RR_MAX_K}, got k={k}, list_len={L}")
             self._ws_faithful = {key: torch.empty(nbytes, dtype=torch.uint8, device=self.device)}
@@ -95,6 +101,14 @@ class _Faithful:
         D = torch.empty((nq, k), dtype=torch.float32, device=self.device) if D is None else D
         I = torch.empty((nq, k), dtype=torch.int64, device=self.device) if I is None else I
         exact = torch.empty(nq, dtype=torch.uint8, device=self.device)
+        if self.exact_l2:
+            bound = torch.empty((nq, 2), dtype=torch.float32, device=self.device)   # (A(q), R(q))
+            check(lib().rr_flat_search_faithful_l2(self._xb.data_ptr(), self._hn.data_ptr() if self._hn is not None else None,
+                                                   _RR_DTYPE[self.dtype], self._xf.data_ptr(), self.d, self._fstats.data_ptr(), n_rows_total,
+                                                   self.d, self.dim, segs, len(segs), xq_half.data_ptr(), xq_f32.data_ptr(), nq, k, L,
+                                                   D.data_ptr(), I.data_ptr(), exact.data_ptr(), bound.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                   mptr, mstride, _stream_ptr()), "rr_flat_search_faithful_l2")
+            return D, I, exact, bound
         eps = torch.empty(nq, dtype=torch.float32, device=self.device)
         check(lib().rr_flat_search_faithful(self._xb.data_ptr(), _RR_DTYPE[self.dtype], self._xf.data_ptr(), self.d, self._fstats.data_ptr(),
                                             n_rows_total, self.d, self.dim, segs, len(segs), xq_half.data_ptr(), xq_f32.data_ptr(), nq, k, L,
@@ -110,15 +124,16 @@ class _Faithful:
                 raise ValueError(f"k must be in [1, {_lib.RR_MAX_K}], got {k}")
             self._ws_exact = {k: torch.empty(nbytes, dtype=torch.uint8, device=self.device)}
             ws = self._ws_exact[k]
-        check(lib().rr_flat_search_f32_exact(self._xf.data_ptr(), self.d, n_rows_total, self.d, segs, len(segs), xq_f32.data_ptr(),
-                                             xq_f32.shape[0], qidx.data_ptr() if qidx is not None else None,
-                                             qidx.numel() if qidx is not None else xq_f32.shape[0], k, D.data_ptr(), I.data_ptr(),
-                                             ws.data_ptr(), ws.numel(), mptr, mstride, _stream_ptr()), "rr_flat_search_f32_exact")
+        name = "rr_flat_search_f32_exact_l2" if self.exact_l2 else "rr_flat_search_f32_exact"
+        check(getattr(lib(), name)(self._xf.data_ptr(), self.d, n_rows_total, self.d, segs, len(segs), xq_f32.data_ptr(),
+                                   xq_f32.shape[0], qidx.data_ptr() if qidx is not None else None,
+                                   qidx.numel() if qidx is not None else xq_f32.shape[0], k, D.data_ptr(), I.data_ptr(),
+                                   ws.data_ptr(), ws.numel(), mptr, mstride, _stream_ptr()), name)
 
     def _faithful_search(self, xq, k, route_mask, out, segs, n_rows_total, mask_args):
         """search_exact_f32, then one host read of the proof flags; unproven queries again at list_len = 1024, then the exact scan."""
         if not (isinstance(xq, tuple) and len(xq) == 2):
-            raise ValueError("an exact_f32 index searches the (half, f32) query pair that prepare_queries() returns")
+            raise ValueError("an exact_f32 / exact_l2 index searches the (half, f32) query pair that prepare_queries() returns")
         xq_half, xq_f32 = xq
         if (xq_half.dtype != self._xb.dtype or xq_half.dim() != 2 or xq_half.shape[1] != self.dim or not xq_half.is_contiguous()
                 or xq_f32.dtype != torch.float32 or xq_f32.shape != (xq_half.shape[0], self.d) or not xq_f32.is_contiguous()):
@@ -180,13 +195,18 @@ class FlatIndex(_Faithful):
     exact_f32=True (ip / cosine): the f32 rows are kept beside the half copy (3x the half bytes) and searches return what the
     reference's IndexFlatIP returns on the UNROUNDED f32 rows and queries, bit for bit with an f64-accumulating CPU scan: the half
     copy only screens (include/ragroute_hip.h rr_flat_search_faithful).  prepare_queries() then returns a (half, f32) pair.
+
+    exact_l2=True (l2): the same mode under the squared-L2 metric — the distances of the reference's IndexFlatL2 on the unrounded
+    f32 rows and queries, nearest first (rr_flat_search_faithful_l2); everything said of an exact_f32 index holds for it.
     """
 
-    def __init__(self, d, metric="ip", dtype="fp16", device=None, exact_f32=False):
+    def __init__(self, d, metric="ip", dtype="fp16", device=None, exact_f32=False, exact_l2=False):
         if metric not in ("ip", "cosine", "l2"):
             raise ValueError(f"unknown metric {metric!r}")
         if exact_f32 and metric == "l2":
             raise ValueError("exact_f32 serves the ip / cosine metrics only")
+        if exact_l2 and metric != "l2":
+            raise ValueError("exact_l2 serves the l2 metric only (ip / cosine: exact_f32)")
         if dtype not in _TORCH_DTYPE:
             raise ValueError(f"unknown dtype {dtype!r}")
         self.d = int(d)
@@ -206,7 +226,8 @@ class FlatIndex(_Faithful):
         self.screen_list = 512
         self.screen_fallbacks = 0
         self.exact_f32 = bool(exact_f32)
-        if self.exact_f32:
+        self.exact_l2 = bool(exact_l2)
+        if self._faith:
             self._faithful_init(0)
 
     # -- storage -----------------------------------------------------------------------------
@@ -215,7 +236,7 @@ class FlatIndex(_Faithful):
             new = torch.empty((n, self.dim), dtype=self._xb.dtype, device=self.device)
             new[: self.ntotal].copy_(self._xb[: self.ntotal])
             self._xb = new
-            if self.exact_f32:
+            if self._faith:
                 newf = torch.empty((n, self.d), dtype=torch.float32, device=self.device)
                 newf[: self.ntotal].copy_(self._xf[: self.ntotal])
                 self._xf = newf
@@ -227,11 +248,12 @@ class FlatIndex(_Faithful):
             raise ValueError(f"expected rows of dimension {self.d}, got {x.shape[1]}")
         if self.ntotal + n > self._xb.shape[0]:
             self.reserve(max(self.ntotal + n, int(self._xb.shape[0] * 1.5)))
-        if self.exact_f32:
+        if self._faith:
             with torch.cuda.device(self.device):
                 self._ingest_f32(x, self._xf[self.ntotal: self.ntotal + n], self._xb[self.ntotal: self.ntotal + n], chunk_rows)
                 self.ntotal += n
                 self._faithful_build(self.ntotal)   # maxima over the whole corpus
+            self._refresh_norms()   # (exact_l2: the scan of the half copy ranks by them)
             return
         with torch.cuda.device(self.device):
             for s in range(0, n, chunk_rows):
@@ -259,8 +281,8 @@ class FlatIndex(_Faithful):
 
     def adopt(self, xb_dev, ntotal=None):
         """Use an existing device matrix [n, dim] of the index dtype as the corpus (no copy)."""
-        if self.exact_f32:
-            raise _lib.RagrouteHipError("adopt() takes a half matrix only; an exact_f32 index ingests its f32 rows with add()")
+        if self._faith:
+            raise _lib.RagrouteHipError("adopt() takes a half matrix only; an exact_f32 / exact_l2 index ingests its f32 rows with add()")
         if xb_dev.dtype != self._xb.dtype or xb_dev.dim() != 2 or xb_dev.shape[1] != self.dim or not xb_dev.is_contiguous():
             raise ValueError("adopt() needs a contiguous device matrix [n, rr_padded_dim(d)] of the index dtype")
         self._xb = xb_dev
@@ -349,8 +371,8 @@ class FlatIndex(_Faithful):
 
     def prepare_queries(self, xq):
         """float32 [nq,d] (numpy or tensor) -> device [nq,dim] in the index dtype (normalised for cosine).
-        exact_f32: the pair (half [nq,dim], f32 [nq,d]) that search_prepared() takes."""
-        if self.exact_f32:
+        exact_f32 / exact_l2: the pair (half [nq,dim], f32 [nq,d]) that search_prepared() takes."""
+        if self._faith:
             return self._prepare_f32(xq)
         if isinstance(xq, np.ndarray):
             xq = torch.from_numpy(np.ascontiguousarray(xq, dtype=np.float32))
@@ -366,8 +388,8 @@ class FlatIndex(_Faithful):
         """Device-to-device search: xq_half [nq,dim] index dtype -> (D f32[nq,k], I i64[nq,k]) CUDA tensors.
         route_mask: optional bool/uint8 CUDA tensor [nq] (may be a strided column of the router's [nq,C] mask):
         queries with a zero entry get an all-padding result.  Enqueued on the current stream, no host sync.
-        exact_f32: xq_half is the (half, f32) pair of prepare_queries(); one host read of the proof flags."""
-        if self.exact_f32:
+        exact_f32 / exact_l2: xq_half is the (half, f32) pair of prepare_queries(); one host read of the proof flags."""
+        if self._faith:
             return self._faithful_search(xq_half, k, route_mask, out, self._segments(id_offset, route_mask), self.ntotal, self._mask_args)
         if xq_half.dtype != self._xb.dtype or xq_half.dim() != 2 or xq_half.shape[1] != self.dim or not xq_half.is_contiguous():
             raise ValueError("search_prepared() needs contiguous [nq, dim] queries of the index dtype")
@@ -402,10 +424,11 @@ class FlatIndex(_Faithful):
 
     def search_exact_f32(self, xq_f32_dev, k, list_len=None, route_mask=None, id_offset=0):
         """exact_f32 index, device to device, no host sync: float32 queries [nq,d] -> (D, I, exact, eps) CUDA tensors.  exact[q] == 1
-        where the top-k is proven on the f32 rows; eps[q] is the bound on the half-precision scan's error for query q.  search()
-        and search_prepared() wrap this with the retry and the exact fallback."""
-        if not self.exact_f32:
-            raise _lib.RagrouteHipError("search_exact_f32() needs an index built with exact_f32=True")
+        where the top-k is proven on the f32 rows; eps[q] is the bound on the half-precision scan's error for query q (an exact_l2
+        index returns the bound [nq, 2] = (A(q), R(q)) in its place).  search() and search_prepared() wrap this with the retry
+        and the exact fallback."""
+        if not self._faith:
+            raise _lib.RagrouteHipError("search_exact_f32() needs an index built with exact_f32=True or exact_l2=True")
         xh, xf = self._prepare_f32(xq_f32_dev)
         L = self._faithful_list_len(k) if list_len is None else int(list_len)
         mptr, mstride = self._mask_args(route_mask, xh.shape[0])
@@ -432,17 +455,20 @@ class SegmentedIndex(_Faithful):
     Metrics: "ip" / "cosine", and "l2" (C ABI `rr_flat_search_segments_l2`: squared L2 distances, nearest first, padding
     (+inf, -1) — the reference's wikipedia federation, ten sources of one DPR encoder whose merge keeps the lowest scores,
     config.py:59-70, rerank.py:28-34); `_hn` then holds |x|^2 / 2 of every matrix row, filled source by source.
-    exact_f32=True (ip / cosine): f32 rows beside the half matrix, results faithful to them (FlatIndex)."""
+    exact_f32=True (ip / cosine), exact_l2=True (l2): f32 rows beside the half matrix, results faithful to them (FlatIndex)."""
 
-    def __init__(self, d, rows_per_source, id_offsets=None, mask_cols=None, metric="ip", dtype="fp16", device=None, exact_f32=False):
+    def __init__(self, d, rows_per_source, id_offsets=None, mask_cols=None, metric="ip", dtype="fp16", device=None, exact_f32=False,
+                 exact_l2=False):
         if metric not in ("ip", "cosine", "l2"):
             raise ValueError(f"unknown metric {metric!r}")
         if exact_f32 and metric == "l2":
             raise ValueError("exact_f32 serves the ip / cosine metrics only")
+        if exact_l2 and metric != "l2":
+            raise ValueError("exact_l2 serves the l2 metric only (ip / cosine: exact_f32)")
         rows = [int(n) for n in rows_per_source]
         if not 1 <= len(rows) <= _lib.RR_MAX_SEGMENTS or min(rows) < 0:
             raise ValueError(f"need 1 .. {_lib.RR_MAX_SEGMENTS} sources with >= 0 rows each")
-        self._proto = FlatIndex(d, metric=metric, dtype=dtype, device=device, exact_f32=exact_f32)   # query conversion, workspace, dims
+        self._proto = FlatIndex(d, metric=metric, dtype=dtype, device=device, exact_f32=exact_f32, exact_l2=exact_l2)   # query conversion, workspace, dims
         self.d, self.dim, self.metric, self.dtype, self.device = self._proto.d, self._proto.dim, metric, dtype, self._proto.device
         self.rows = rows
         self.id_offsets = [int(v) for v in (id_offsets if id_offsets is not None else [s << 40 for s in range(len(rows))])]
@@ -464,7 +490,8 @@ class SegmentedIndex(_Faithful):
         # metric "l2": |x|^2 / 2 of every matrix row, aligned with _xb (alignment gaps: unspecified, never used)
         self._hn = torch.zeros(max(1, self.n_rows_total), dtype=torch.float32, device=self.device) if metric == "l2" else None
         self.exact_f32 = bool(exact_f32)
-        if self.exact_f32:
+        self.exact_l2 = bool(exact_l2)
+        if self._faith:
             self._faithful_init(self.n_rows_total)
 
     def rows_of(self, s):
@@ -500,10 +527,11 @@ class SegmentedIndex(_Faithful):
         if x.shape[0] != self.rows[s] or x.shape[1] != self.d:
             raise ValueError(f"source {s} holds [{self.rows[s]}, {self.d}] rows")
         out = self.rows_of(s)
-        if self.exact_f32:
+        if self._faith:
             with torch.cuda.device(self.device):
                 self._ingest_f32(x, self._xf[self.begins[s]: self.begins[s] + self.rows[s]], out, chunk_rows)
                 self._faithful_build(self.n_rows_total)
+            self.refresh_norms(s)
             return
         with torch.cuda.device(self.device):
             for b in range(0, x.shape[0], chunk_rows):
@@ -525,8 +553,8 @@ class SegmentedIndex(_Faithful):
                 raise ValueError("sources of one SegmentedIndex share dimension, metric, dtype and device")
         seg = cls(first.d, [i.ntotal for i in indexes], id_offsets, mask_cols, first.metric, first.dtype, first.device)
         for s, i in enumerate(indexes):
-            if i.exact_f32:
-                raise _lib.RagrouteHipError("from_indexes() packs half matrices only; an exact_f32 index ingests its f32 rows with fill()")
+            if i._faith:
+                raise _lib.RagrouteHipError("from_indexes() packs half matrices only; an exact_f32 / exact_l2 index ingests its f32 rows with fill()")
             seg.rows_of(s).copy_(i.xb)
             if first.metric == "l2" and i.ntotal:
                 seg.norms_of(s).copy_(i._hn[: i.ntotal])
@@ -539,8 +567,8 @@ class SegmentedIndex(_Faithful):
     def search_prepared(self, xq_half, k, route_mask=None, out=None):
         """xq_half [nq, dim] index dtype -> (D f32 [nq,k], I i64 [nq,k]) CUDA tensors: the merged top-k over the selected sources.
         route_mask: optional bool/uint8 CUDA matrix [nq, C] (the router's mask; source s reads column mask_cols[s]).
-        exact_f32: xq_half is the (half, f32) pair of prepare_queries()."""
-        if self.exact_f32:
+        exact_f32 / exact_l2: xq_half is the (half, f32) pair of prepare_queries()."""
+        if self._faith:
             return self._faithful_search(xq_half, k, route_mask, out, self._segs, self.n_rows_total, self._mask_args)
         if xq_half.dtype != self._xb.dtype or xq_half.dim() != 2 or xq_half.shape[1] != self.dim or not xq_half.is_contiguous():
             raise ValueError("search_prepared() needs contiguous [nq, dim] queries of the index dtype")
@@ -573,8 +601,8 @@ class SegmentedIndex(_Faithful):
 
     def search_exact_f32(self, xq_f32_dev, k, list_len=None, route_mask=None):
         """As FlatIndex.search_exact_f32, over the segments (route_mask [nq, C] as search_prepared)."""
-        if not self.exact_f32:
-            raise _lib.RagrouteHipError("search_exact_f32() needs an index built with exact_f32=True")
+        if not self._faith:
+            raise _lib.RagrouteHipError("search_exact_f32() needs an index built with exact_f32=True or exact_l2=True")
         xh, xf = self._prepare_f32(xq_f32_dev)
         L = self._faithful_list_len(k) if list_len is None else int(list_len)
         mptr, mstride = self._mask_args(route_mask, xh.shape[0])
