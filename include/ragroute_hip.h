@@ -55,7 +55,12 @@ int rr_l2_normalize_f32(float* d_x, int64_t n, int64_t d, void* stream);
  * Stands in for what `faiss.read_index` leaves in memory — reference
  * ragroute/data_source.py:69-80 — and is also used to prepare query batches
  * (data_source.py:113-114 builds the f32 [1,d] query).
- * d_x: device f32, n rows of d values, row stride ld_in; d_out: device [n][d_out] halves. */
+ * d_x: device f32, n rows of d values, row stride ld_in >= d (any alignment); d_out: device [n][d_out] halves, d_out >= d.
+ * The conversion rounds to nearest-even on every path (16-byte or scalar, chosen per row by alignment): ties to the even
+ * neighbour, fp16 overflow to inf from 65520 on, fp16 / bf16 subnormal results kept, f32 subnormal inputs honoured, the sign of
+ * zero kept, NaN in = NaN out (payload unspecified); columns d .. d_out are +0.  With normalize, the row is scaled in f32 as
+ * rr_l2_normalize_f32 does (zero, underflowing and NaN norms leave it unchanged) and the f32 product is converted.  Pinned bit
+ * for bit on every fp16 / bf16 value, tie and threshold by tests/test_ingest_gpu.py. */
 int rr_rows_to_half(const float* d_x, int64_t n, int64_t d, int64_t ld_in, void* d_out, int dtype,
                     int64_t d_out_dim, int normalize, void* stream);
 

@@ -41,6 +41,15 @@ __global__ __launch_bounds__(256) void l2_normalize_f32_kernel(float* x, int64_t
   }
 }
 
+// f32 -> f16 / bf16, round to nearest-even, of a value that is ALREADY rounded to f32.  The empty asm keeps the conversion apart
+// from the multiplication that made v: hipcc otherwise fuses the two into v_fma_mixlo_f16 v, x, inv, 0, whose +0 addend turns a
+// -0 product into +0 (seen on the scalar path, fp16: tests/test_ingest_gpu.py pins the sign of zero on every path).
+template <typename T>
+__device__ __forceinline__ T round_to(float v) {
+  asm("" : "+v"(v));
+  return (T)v;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void rows_to_half_kernel(const float* x, int64_t n, int64_t d, int64_t ld_in, T* out,
                                                            int64_t d_out, int normalize) {
@@ -63,12 +72,12 @@ __global__ __launch_bounds__(256) void rows_to_half_kernel(const float* x, int64
         vec4 h = {(T)0.f, (T)0.f, (T)0.f, (T)0.f};
         if (i < d / 4) {
           const float4 v = x4[i];
-          h = vec4{(T)(v.x * inv), (T)(v.y * inv), (T)(v.z * inv), (T)(v.w * inv)};
+          h = vec4{round_to<T>(v.x * inv), round_to<T>(v.y * inv), round_to<T>(v.z * inv), round_to<T>(v.w * inv)};
         }
         o4[i] = h;
       }
     } else {
-      for (int64_t i = lane; i < d_out; i += 64) o[i] = i < d ? (T)(xr[i] * inv) : (T)0.f;
+      for (int64_t i = lane; i < d_out; i += 64) o[i] = i < d ? round_to<T>(xr[i] * inv) : (T)0.f;
     }
   }
 }
