@@ -4,47 +4,77 @@ Mirrors the operator surface the reference uses from `faiss` (ragroute/data_sour
   index.search(xq: float32[nq,d], k) -> (D float32[nq,k], I int64[nq,k])      data_source.py:158,186,203
   index.ntotal, index.d
   normalize_L2(x: float32[n,d])  in place                                       data_source.py:198-199
-PyTorch is used for device memory and streams only; all arithmetic is in libragroute_hip.so.
+PyTorch is used for device memory and streams only; all arithmetic is in libragroute_hip.so (reached through _calls.py).
 """
 import numpy as np
 import torch
 
+from . import _calls
 from . import _lib
 from ._lib import check, lib
 
-_TORCH_DTYPE = {"fp16": torch.float16, "bf16": torch.bfloat16}
-_RR_DTYPE = {"fp16": _lib.RR_DTYPE_F16, "bf16": _lib.RR_DTYPE_BF16}
+_K_RANGE = f"k must be in [1, {_lib.RR_MAX_K}], got {{0}}"
+_LIST_RANGE = f"need 1 <= k <= list_len <= {_lib.RR_MAX_K}, got k={{0}}, list_len={{1}}"
 
 
-def _stream_ptr():
-    return torch.cuda.current_stream().cuda_stream
+def normalize_L2(x):
+    """In-place row-wise L2 normalisation (faiss.normalize_L2, data_source.py:198-199).
+    Accepts a C-contiguous float32 numpy array [n,d] (normalised in place through the GPU) or a
+    float32 CUDA tensor (normalised in place on device)."""
+    if isinstance(x, torch.Tensor):
+        if x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous() or x.dim() != 2:
+            raise ValueError("normalize_L2 needs a contiguous float32 CUDA tensor [n,d]")
+        _calls.l2_normalize_(x)
+        return
+    if not (isinstance(x, np.ndarray) and x.dtype == np.float32 and x.ndim == 2 and x.flags.c_contiguous):
+        raise ValueError("normalize_L2 needs a C-contiguous float32 array [n,d]")
+    _calls.require_gpu()
+    t = torch.from_numpy(x).cuda()
+    _calls.l2_normalize_(t)
+    x[...] = t.cpu().numpy()
 
 
-def _require_gpu():
-    if not torch.cuda.is_available():
-        raise _lib.RagrouteHipError("ragroute_amd needs a HIP device (torch.cuda.is_available() is False); there is no CPU fallback")
+class _Index:
+    """What FlatIndex and SegmentedIndex share: the dimensions, metric, dtype and device, the query preparation, the scan workspace,
+    the half-precision search of a half matrix `_xb` (with `_hn`, its half squared norms, under "l2") and the f32-faithful mode.
+    A subclass owns the storage and says what differs: `_segments()`, its segment table; `_n_rows`, the matrix rows it scans;
+    `_mask_args()`, the check of its route mask (a vector per index, a matrix per segmented one).
 
+    The f32-faithful mode (exact_f32=True; C ABI rr_flat_search_faithful; under the squared-L2 metric exact_l2=True and
+    rr_flat_search_faithful_l2, which also reads `_hn`): the f32 rows `_xf` beside the half copy `_xb`, their error / norm maxima
+    `_fstats`, and the search that proves every query's top-k on the f32 rows — a query whose proof fails is repeated with a list
+    of 1024 rows (`faithful_retries` counts those queries), and what is still unproven is answered by the exact f32 scan
+    (`faithful_fallbacks`)."""
 
-def _as_f32_rows(part, device):
-    """A chunk of f32 rows (numpy, np.memmap or tensor) as a contiguous float32 tensor on `device`."""
-    if isinstance(part, np.ndarray):  # also np.memmap: only this chunk is paged in
-        part = np.ascontiguousarray(part, dtype=np.float32)
-        part = torch.from_numpy(part if part.flags.writeable else part.copy())
-    return part.to(device, dtype=torch.float32).contiguous()
-
-
-class _Faithful:
-    """The f32-faithful mode shared by FlatIndex and SegmentedIndex (exact_f32=True; C ABI rr_flat_search_faithful; under the
-    squared-L2 metric exact_l2=True and rr_flat_search_faithful_l2, which also reads the half squared norms `_hn`): the f32 rows
-    `_xf` beside the half copy `_xb`, their error / norm maxima `_fstats`, and the search that proves every query's top-k on the
-    f32 rows — a query whose proof fails is repeated with a list of 1024 rows (`faithful_retries` counts those queries), and
-    what is still unproven is answered by the exact f32 scan (`faithful_fallbacks`)."""
+    def __init__(self, d, metric, dtype, device, exact_f32, exact_l2):
+        if metric not in ("ip", "cosine", "l2"):
+            raise ValueError(f"unknown metric {metric!r}")
+        if exact_f32 and metric == "l2":
+            raise ValueError("exact_f32 serves the ip / cosine metrics only")
+        if exact_l2 and metric != "l2":
+            raise ValueError("exact_l2 serves the l2 metric only (ip / cosine: exact_f32)")
+        if dtype not in _calls.TORCH_DTYPE:
+            raise ValueError(f"unknown dtype {dtype!r}")
+        self.d = int(d)
+        self.metric = metric
+        self.dtype = dtype
+        self.dim = lib().rr_padded_dim(self.d)
+        if self.dim < 0:
+            raise _lib.RagrouteHipError(f"embedding dimension {d} is not supported (max 8192)")
+        _calls.require_gpu()
+        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.exact_f32 = bool(exact_f32)
+        self.exact_l2 = bool(exact_l2)
+        self._hn = None  # |x|^2/2 per matrix row (metric "l2")
+        self._ws = {}
 
     @property
     def _faith(self):
         return self.exact_f32 or self.exact_l2
 
     def _faithful_init(self, n_rows):
+        if not self._faith:
+            return
         self._xf = torch.zeros((max(1, n_rows), self.d), dtype=torch.float32, device=self.device)
         self._fstats = torch.zeros(4, dtype=torch.float32, device=self.device)
         self._ws_faithful = {}
@@ -53,94 +83,100 @@ class _Faithful:
         self.faithful_retries = 0
         self.faithful_fallbacks = 0
 
-    def _ingest_f32(self, x, out_f, out_h, chunk_rows):
-        """f32 rows -> out_f (normalised for cosine by rr_l2_normalize_f32) -> the half copy out_h derived from those rows."""
+    # -- ingest ------------------------------------------------------------------------------
+    def _ingest(self, x, row0, chunk_rows):
+        """f32 rows (numpy, np.memmap or tensor) -> matrix rows [row0, row0 + n) of the half copy, normalised for cosine.  Faithful: the
+        f32 rows go to `_xf` first (normalised by rr_l2_normalize_f32) and the half copy is derived from what lies there."""
         for s in range(0, x.shape[0], chunk_rows):
-            e = min(x.shape[0], s + chunk_rows)
-            f, h = out_f[s:e], out_h[s:e]
-            f.copy_(_as_f32_rows(x[s:e], self.device))
-            if self.metric == "cosine":
-                check(lib().rr_l2_normalize_f32(f.data_ptr(), e - s, self.d, _stream_ptr()), "rr_l2_normalize_f32")
-            check(lib().rr_rows_to_half(f.data_ptr(), e - s, self.d, self.d, h.data_ptr(), _RR_DTYPE[self.dtype], self.dim, 0,
-                                        _stream_ptr()), "rr_rows_to_half")
+            part = _calls.f32_rows(x[s: s + chunk_rows], self.device)
+            lo, hi = row0 + s, row0 + s + part.shape[0]
+            if self._faith:
+                f = self._xf[lo:hi]
+                f.copy_(part)
+                if self.metric == "cosine":
+                    _calls.l2_normalize_(f)
+                _calls.rows_to_half(f, self.dim, self._xb.dtype, False, self._xb[lo:hi])
+            else:
+                _calls.rows_to_half(part, self.dim, self._xb.dtype, self.metric == "cosine", self._xb[lo:hi])
+            del part   # before the next chunk is staged
 
-    def _faithful_build(self, n_rows):
-        check(lib().rr_faithful_build(self._xf.data_ptr(), self.d, self._xb.data_ptr(), _RR_DTYPE[self.dtype], n_rows, self.d, self.dim,
-                                      self._fstats.data_ptr(), _stream_ptr()), "rr_faithful_build")
+    def _faithful_build(self):
+        """Faithful: the maxima over the whole matrix."""
+        if self._faith:
+            check(lib().rr_faithful_build(self._xf.data_ptr(), self.d, self._xb.data_ptr(), _calls.RR_DTYPE[self.dtype], self._n_rows, self.d,
+                                          self.dim, self._fstats.data_ptr(), _calls.stream_ptr()), "rr_faithful_build")
 
-    def _prepare_f32(self, xq):
-        """float32 [nq,d] -> (half [nq,dim], f32 [nq,d]) device queries (both normalised by the library for cosine)."""
-        if isinstance(xq, np.ndarray):
-            xq = torch.from_numpy(np.ascontiguousarray(xq, dtype=np.float32))
-        if xq.dim() != 2 or xq.shape[1] != self.d:
-            raise ValueError(f"queries must be [nq,{self.d}]")
-        xf = xq.to(self.device, dtype=torch.float32).contiguous()
+    # -- queries, workspace, the half-precision search ------------------------------------------
+    def prepare_queries(self, xq):
+        """float32 [nq,d] (numpy or tensor) -> device [nq,dim] in the index dtype (normalised for cosine).
+        exact_f32 / exact_l2: the pair (half [nq,dim], f32 [nq,d]) that search_prepared() takes (both normalised for cosine)."""
+        xf = _calls.f32_queries(xq, self.d, self.device)
+        if not self._faith:
+            return _calls.rows_to_half(xf, self.dim, self._xb.dtype, self.metric == "cosine")
         if self.metric == "cosine":
             xf = xf.clone()
-            check(lib().rr_l2_normalize_f32(xf.data_ptr(), xf.shape[0], self.d, _stream_ptr()), "rr_l2_normalize_f32")
-        xh = torch.empty((xf.shape[0], self.dim), dtype=self._xb.dtype, device=self.device)
-        check(lib().rr_rows_to_half(xf.data_ptr(), xf.shape[0], self.d, self.d, xh.data_ptr(), _RR_DTYPE[self.dtype], self.dim, 0,
-                                    _stream_ptr()), "rr_rows_to_half")
-        return xh, xf
+            _calls.l2_normalize_(xf)
+        return _calls.rows_to_half(xf, self.dim, self._xb.dtype, False), xf
 
+    def _workspace(self, k):
+        return _calls.workspace(self._ws, k, self.device, _K_RANGE, "rr_flat_search_workspace_bytes_for", k, self.dim)
+
+    def _half_search(self, xq_half, k, route_mask, out, n_rows, id_offset=0, segs=None):
+        """Checked prepared queries -> (D, I): rr_flat_search / _l2 over n_rows rows, or their segmented forms over the table `segs`."""
+        nq = xq_half.shape[0]
+        ws = self._workspace(k)
+        D, I = _calls.out_pair(nq, k, self.device, out)
+        mptr, mstride = self._mask_args(route_mask, nq)
+        _calls.half_search(self._xb, n_rows, xq_half, k, D, I, ws, mptr, mstride, id_offset, segs, self.metric == "l2", self._hn)
+        return D, I
+
+    # -- the f32-faithful search ---------------------------------------------------------------
     def _faithful_list_len(self, k):
         L = self.faithful_list if self.faithful_list is not None else min(_lib.RR_MAX_K, max(256, 4 * k))
         return max(int(L), k)
 
     def _faithful_raw(self, xq_half, xq_f32, k, L, segs, n_rows_total, mptr, mstride, D=None, I=None):
         nq = xq_half.shape[0]
-        key = (k, L, nq)
-        ws = self._ws_faithful.get(key)
-        if ws is None:
-            query = lib().rr_flat_search_faithful_l2_workspace_bytes if self.exact_l2 else lib().rr_flat_search_faithful_workspace_bytes
-            nbytes = query(k, L, nq, self.dim)
-            if nbytes == 0:
-                raise ValueError(f"need 1 <= k <= list_len <= {_lib.RR_MAX_K}, got k={k}, list_len={L}")
-            self._ws_faithful = {key: torch.empty(nbytes, dtype=torch.uint8, device=self.device)}
-            ws = self._ws_faithful[key]
-        D = torch.empty((nq, k), dtype=torch.float32, device=self.device) if D is None else D
-        I = torch.empty((nq, k), dtype=torch.int64, device=self.device) if I is None else I
+        ws = _calls.workspace(self._ws_faithful, (k, L, nq), self.device, _LIST_RANGE,
+                              "rr_flat_search_faithful_l2_workspace_bytes" if self.exact_l2 else "rr_flat_search_faithful_workspace_bytes",
+                              k, L, nq, self.dim)
+        D, I = _calls.out_pair(nq, k, self.device, None if D is None else (D, I))
         exact = torch.empty(nq, dtype=torch.uint8, device=self.device)
         if self.exact_l2:
             bound = torch.empty((nq, 2), dtype=torch.float32, device=self.device)   # (A(q), R(q))
             check(lib().rr_flat_search_faithful_l2(self._xb.data_ptr(), self._hn.data_ptr() if self._hn is not None else None,
-                                                   _RR_DTYPE[self.dtype], self._xf.data_ptr(), self.d, self._fstats.data_ptr(), n_rows_total,
+                                                   _calls.RR_DTYPE[self.dtype], self._xf.data_ptr(), self.d, self._fstats.data_ptr(), n_rows_total,
                                                    self.d, self.dim, segs, len(segs), xq_half.data_ptr(), xq_f32.data_ptr(), nq, k, L,
                                                    D.data_ptr(), I.data_ptr(), exact.data_ptr(), bound.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                   mptr, mstride, _stream_ptr()), "rr_flat_search_faithful_l2")
+                                                   mptr, mstride, _calls.stream_ptr()), "rr_flat_search_faithful_l2")
             return D, I, exact, bound
         eps = torch.empty(nq, dtype=torch.float32, device=self.device)
-        check(lib().rr_flat_search_faithful(self._xb.data_ptr(), _RR_DTYPE[self.dtype], self._xf.data_ptr(), self.d, self._fstats.data_ptr(),
+        check(lib().rr_flat_search_faithful(self._xb.data_ptr(), _calls.RR_DTYPE[self.dtype], self._xf.data_ptr(), self.d, self._fstats.data_ptr(),
                                             n_rows_total, self.d, self.dim, segs, len(segs), xq_half.data_ptr(), xq_f32.data_ptr(), nq, k, L,
                                             D.data_ptr(), I.data_ptr(), exact.data_ptr(), eps.data_ptr(), ws.data_ptr(), ws.numel(), mptr,
-                                            mstride, _stream_ptr()), "rr_flat_search_faithful")
+                                            mstride, _calls.stream_ptr()), "rr_flat_search_faithful")
         return D, I, exact, eps
 
     def _exact_scan(self, xq_f32, qidx, k, segs, n_rows_total, mptr, mstride, D, I):
-        ws = self._ws_exact.get(k)
-        if ws is None:
-            nbytes = lib().rr_flat_search_f32_exact_workspace_bytes(k, self.d)
-            if nbytes == 0:
-                raise ValueError(f"k must be in [1, {_lib.RR_MAX_K}], got {k}")
-            self._ws_exact = {k: torch.empty(nbytes, dtype=torch.uint8, device=self.device)}
-            ws = self._ws_exact[k]
+        ws = _calls.workspace(self._ws_exact, k, self.device, _K_RANGE, "rr_flat_search_f32_exact_workspace_bytes", k, self.d)
         name = "rr_flat_search_f32_exact_l2" if self.exact_l2 else "rr_flat_search_f32_exact"
         check(getattr(lib(), name)(self._xf.data_ptr(), self.d, n_rows_total, self.d, segs, len(segs), xq_f32.data_ptr(),
                                    xq_f32.shape[0], qidx.data_ptr() if qidx is not None else None,
                                    qidx.numel() if qidx is not None else xq_f32.shape[0], k, D.data_ptr(), I.data_ptr(),
-                                   ws.data_ptr(), ws.numel(), mptr, mstride, _stream_ptr()), name)
+                                   ws.data_ptr(), ws.numel(), mptr, mstride, _calls.stream_ptr()), name)
 
-    def _faithful_search(self, xq, k, route_mask, out, segs, n_rows_total, mask_args):
+    def _faithful_search(self, xq, k, route_mask, out, segs, n_rows_total):
         """search_exact_f32, then one host read of the proof flags; unproven queries again at list_len = 1024, then the exact scan."""
         if not (isinstance(xq, tuple) and len(xq) == 2):
             raise ValueError("an exact_f32 / exact_l2 index searches the (half, f32) query pair that prepare_queries() returns")
         xq_half, xq_f32 = xq
-        if (xq_half.dtype != self._xb.dtype or xq_half.dim() != 2 or xq_half.shape[1] != self.dim or not xq_half.is_contiguous()
-                or xq_f32.dtype != torch.float32 or xq_f32.shape != (xq_half.shape[0], self.d) or not xq_f32.is_contiguous()):
-            raise ValueError("search_prepared() needs the contiguous ([nq, dim] index dtype, [nq, d] float32) pair of prepare_queries()")
+        pair = "search_prepared() needs the contiguous ([nq, dim] index dtype, [nq, d] float32) pair of prepare_queries()"
+        _calls.check_half_queries(xq_half, self._xb.dtype, self.dim, pair)
+        if xq_f32.dtype != torch.float32 or xq_f32.shape != (xq_half.shape[0], self.d) or not xq_f32.is_contiguous():
+            raise ValueError(pair)
         nq = xq_half.shape[0]
         D, I = out if out is not None else (None, None)
-        mptr, mstride = mask_args(route_mask, nq)
+        mptr, mstride = self._mask_args(route_mask, nq)
         D, I, exact, _ = self._faithful_raw(xq_half, xq_f32, k, self._faithful_list_len(k), segs, n_rows_total, mptr, mstride, D, I)
         if nq == 0:
             return D, I
@@ -151,7 +187,7 @@ class _Faithful:
         still = bad
         if self._faithful_list_len(k) < _lib.RR_MAX_K:
             sub_mask = route_mask[bad].contiguous() if route_mask is not None else None
-            smptr, smstride = mask_args(sub_mask, int(bad.numel()))
+            smptr, smstride = self._mask_args(sub_mask, int(bad.numel()))
             D2, I2, ex2, _ = self._faithful_raw(xq_half[bad].contiguous(), xq_f32[bad].contiguous(), k, _lib.RR_MAX_K, segs, n_rows_total,
                                                 smptr, smstride)
             D[bad] = D2
@@ -162,25 +198,28 @@ class _Faithful:
             self._exact_scan(xq_f32, still.to(torch.int32).contiguous(), k, segs, n_rows_total, mptr, mstride, D, I)
         return D, I
 
+    def search_exact_f32(self, xq_f32_dev, k, list_len=None, route_mask=None, id_offset=0):
+        """exact_f32 index, device to device, no host sync: float32 queries [nq,d] -> (D, I, exact, eps) CUDA tensors.  exact[q] == 1
+        where the top-k is proven on the f32 rows; eps[q] is the bound on the half-precision scan's error for query q (an exact_l2
+        index returns the bound [nq, 2] = (A(q), R(q)) in its place).  search() and search_prepared() wrap this with the retry
+        and the exact fallback."""
+        if not self._faith:
+            raise _lib.RagrouteHipError("search_exact_f32() needs an index built with exact_f32=True or exact_l2=True")
+        xh, xf = self.prepare_queries(xq_f32_dev)
+        L = self._faithful_list_len(k) if list_len is None else int(list_len)
+        mptr, mstride = self._mask_args(route_mask, xh.shape[0])
+        return self._faithful_raw(xh, xf, int(k), L, self._segments(id_offset, route_mask), self._n_rows, mptr, mstride)
 
-def normalize_L2(x):
-    """In-place row-wise L2 normalisation (faiss.normalize_L2, data_source.py:198-199).
-    Accepts a C-contiguous float32 numpy array [n,d] (normalised in place through the GPU) or a
-    float32 CUDA tensor (normalised in place on device)."""
-    if isinstance(x, torch.Tensor):
-        if x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous() or x.dim() != 2:
-            raise ValueError("normalize_L2 needs a contiguous float32 CUDA tensor [n,d]")
-        check(lib().rr_l2_normalize_f32(x.data_ptr(), x.shape[0], x.shape[1], _stream_ptr()), "rr_l2_normalize_f32")
-        return
-    if not (isinstance(x, np.ndarray) and x.dtype == np.float32 and x.ndim == 2 and x.flags.c_contiguous):
-        raise ValueError("normalize_L2 needs a C-contiguous float32 array [n,d]")
-    _require_gpu()
-    t = torch.from_numpy(x).cuda()
-    check(lib().rr_l2_normalize_f32(t.data_ptr(), x.shape[0], x.shape[1], _stream_ptr()), "rr_l2_normalize_f32")
-    x[...] = t.cpu().numpy()
+    def search(self, xq, k, route_mask=None):
+        """float32 [nq,d] -> (D float32[nq,k], I int64[nq,k]) numpy arrays; route_mask (tensor or array) as search_prepared()."""
+        with torch.cuda.device(self.device):
+            if route_mask is not None and not isinstance(route_mask, torch.Tensor):
+                route_mask = torch.from_numpy(np.ascontiguousarray(route_mask, dtype=np.uint8)).to(self.device)
+            D, I = self.search_prepared(self.prepare_queries(xq), int(k), route_mask=route_mask)
+            return D.cpu().numpy(), I.cpu().numpy()
 
 
-class FlatIndex(_Faithful):
+class FlatIndex(_Index):
     """Exact inner-product index (the role of faiss.IndexFlatIP in the reference).
 
     metric: "ip" (reference behaviour), "cosine" (rows and queries L2-normalised on ingest/search, i.e. normalize_L2 + IP
@@ -201,34 +240,30 @@ class FlatIndex(_Faithful):
     """
 
     def __init__(self, d, metric="ip", dtype="fp16", device=None, exact_f32=False, exact_l2=False):
-        if metric not in ("ip", "cosine", "l2"):
-            raise ValueError(f"unknown metric {metric!r}")
-        if exact_f32 and metric == "l2":
-            raise ValueError("exact_f32 serves the ip / cosine metrics only")
-        if exact_l2 and metric != "l2":
-            raise ValueError("exact_l2 serves the l2 metric only (ip / cosine: exact_f32)")
-        if dtype not in _TORCH_DTYPE:
-            raise ValueError(f"unknown dtype {dtype!r}")
-        self.d = int(d)
-        self.metric = metric
-        self.dtype = dtype
-        self.dim = lib().rr_padded_dim(self.d)
-        if self.dim < 0:
-            raise _lib.RagrouteHipError(f"embedding dimension {d} is not supported (max 8192)")
-        _require_gpu()
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        super().__init__(d, metric, dtype, device, exact_f32, exact_l2)
         self.ntotal = 0
-        self._xb = torch.empty((0, self.dim), dtype=_TORCH_DTYPE[dtype], device=self.device)
-        self._hn = None  # |x|^2/2 per row (metric "l2")
-        self._ws = {}
+        self._xb = torch.empty((0, self.dim), dtype=_calls.TORCH_DTYPE[dtype], device=self.device)
         self._x8 = self._x8_stats = None   # int8 screening copy (build_screen)
         self._ws_screen = {}
         self.screen_list = 512
         self.screen_fallbacks = 0
-        self.exact_f32 = bool(exact_f32)
-        self.exact_l2 = bool(exact_l2)
-        if self._faith:
-            self._faithful_init(0)
+        self._faithful_init(0)
+
+    @property
+    def _n_rows(self):
+        return self.ntotal
+
+    def _segments(self, id_offset=0, route_mask=None):
+        """The faithful modes' one-entry segment table (the plain search never goes through it)."""
+        return (_lib.SegmentStruct * 1)(_lib.SegmentStruct(0, self.ntotal, int(id_offset), 0 if route_mask is not None else -1, 0))
+
+    @staticmethod
+    def _mask_args(route_mask, nq):
+        if route_mask is None:
+            return None, 0
+        if route_mask.dtype not in (torch.bool, torch.uint8) or route_mask.dim() != 1 or route_mask.shape[0] != nq or not route_mask.is_cuda:
+            raise ValueError("route_mask must be a bool/uint8 CUDA vector with one entry per query")
+        return route_mask.data_ptr(), route_mask.stride(0)
 
     # -- storage -----------------------------------------------------------------------------
     def reserve(self, n):
@@ -248,36 +283,19 @@ class FlatIndex(_Faithful):
             raise ValueError(f"expected rows of dimension {self.d}, got {x.shape[1]}")
         if self.ntotal + n > self._xb.shape[0]:
             self.reserve(max(self.ntotal + n, int(self._xb.shape[0] * 1.5)))
-        if self._faith:
-            with torch.cuda.device(self.device):
-                self._ingest_f32(x, self._xf[self.ntotal: self.ntotal + n], self._xb[self.ntotal: self.ntotal + n], chunk_rows)
-                self.ntotal += n
-                self._faithful_build(self.ntotal)   # maxima over the whole corpus
-            self._refresh_norms()   # (exact_l2: the scan of the half copy ranks by them)
-            return
         with torch.cuda.device(self.device):
-            for s in range(0, n, chunk_rows):
-                e = min(n, s + chunk_rows)
-                part = x[s:e]
-                if isinstance(part, np.ndarray):  # also np.memmap: only this chunk is paged in
-                    part = np.ascontiguousarray(part, dtype=np.float32)
-                    part = torch.from_numpy(part if part.flags.writeable else part.copy())
-                part = part.to(self.device, dtype=torch.float32).contiguous()
-                out = self._xb[self.ntotal + s : self.ntotal + e]
-                check(lib().rr_rows_to_half(part.data_ptr(), e - s, self.d, self.d, out.data_ptr(), _RR_DTYPE[self.dtype],
-                                            self.dim, int(self.metric == "cosine"), _stream_ptr()), "rr_rows_to_half")
-                del part
-        self.ntotal += n
+            self._ingest(x, self.ntotal, chunk_rows)
+            self.ntotal += n
+            self._faithful_build()
         self._x8 = self._x8_stats = None  # one scale for the whole corpus: the screening copy is rebuilt, not appended to
-        self._refresh_norms()
+        self._refresh_norms()   # (exact_l2 too: the scan of the half copy ranks by them)
 
     def _refresh_norms(self):
         if self.metric != "l2":
             return
         self._hn = torch.empty(max(1, self.ntotal), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            check(lib().rr_half_sqnorms(self._xb.data_ptr(), _RR_DTYPE[self.dtype], self.ntotal, self.dim, self._hn.data_ptr(),
-                                        _stream_ptr()), "rr_half_sqnorms")
+            _calls.half_sqnorms(self._xb, self.ntotal, self._hn)
 
     def adopt(self, xb_dev, ntotal=None):
         """Use an existing device matrix [n, dim] of the index dtype as the corpus (no copy)."""
@@ -305,8 +323,8 @@ class FlatIndex(_Faithful):
         self._x8 = torch.empty((max(1, self.ntotal), dim8), dtype=torch.int8, device=self.device)
         self._x8_stats = torch.zeros(8, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            check(lib().rr_screen_build(self._xb.data_ptr(), _RR_DTYPE[self.dtype], self.ntotal, self.dim, self._x8.data_ptr(),
-                                        self._x8_stats.data_ptr(), _stream_ptr()), "rr_screen_build")
+            check(lib().rr_screen_build(self._xb.data_ptr(), _calls.RR_DTYPE[self.dtype], self.ntotal, self.dim, self._x8.data_ptr(),
+                                        self._x8_stats.data_ptr(), _calls.stream_ptr()), "rr_screen_build")
         return self
 
     def search_screened(self, xq_half, k, id_offset=0, out=None, route_mask=None, list_len=None):
@@ -317,41 +335,23 @@ class FlatIndex(_Faithful):
         nq = xq_half.shape[0]
         L = int(list_len if list_len is not None else min(_lib.RR_MAX_K, max(self.screen_list, 16 * k)))
         L = max(L, k)
-        key = (k, L, nq)
-        ws = self._ws_screen.get(key)
-        if ws is None:
-            nbytes = lib().rr_flat_search_screened_workspace_bytes(k, L, nq, self.dim)
-            if nbytes == 0:
-                raise ValueError(f"need 1 <= k <= list_len <= {_lib.RR_MAX_K}, got k={k}, list_len={L}")
-            self._ws_screen = {key: torch.empty(nbytes, dtype=torch.uint8, device=self.device)}
-            ws = self._ws_screen[key]
-        if out is None:
-            D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-            I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        else:
-            D, I = out
+        ws = _calls.workspace(self._ws_screen, (k, L, nq), self.device, _LIST_RANGE, "rr_flat_search_screened_workspace_bytes",
+                              k, L, nq, self.dim)
+        D, I = _calls.out_pair(nq, k, self.device, out)
         exact = torch.empty(nq, dtype=torch.uint8, device=self.device)
         mptr, mstride = self._mask_args(route_mask, nq)
-        check(lib().rr_flat_search_screened(self._xb.data_ptr(), _RR_DTYPE[self.dtype], self._x8.data_ptr(), self._x8_stats.data_ptr(),
+        check(lib().rr_flat_search_screened(self._xb.data_ptr(), _calls.RR_DTYPE[self.dtype], self._x8.data_ptr(), self._x8_stats.data_ptr(),
                                             self.ntotal, self.dim, xq_half.data_ptr(), nq, k, L, D.data_ptr(), I.data_ptr(), id_offset,
-                                            exact.data_ptr(), ws.data_ptr(), ws.numel(), mptr, mstride, _stream_ptr()),
+                                            exact.data_ptr(), ws.data_ptr(), ws.numel(), mptr, mstride, _calls.stream_ptr()),
               "rr_flat_search_screened")
         return D, I, exact
-
-    @staticmethod
-    def _mask_args(route_mask, nq):
-        if route_mask is None:
-            return None, 0
-        if route_mask.dtype not in (torch.bool, torch.uint8) or route_mask.dim() != 1 or route_mask.shape[0] != nq or not route_mask.is_cuda:
-            raise ValueError("route_mask must be a bool/uint8 CUDA vector with one entry per query")
-        return route_mask.data_ptr(), route_mask.stride(0)
 
     def centroid(self):
         """float32 CUDA vector [d]: mean of the stored rows (the router's centroid feature, router.py:147-151)."""
         out = torch.empty(self.dim, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            check(lib().rr_centroid(self._xb.data_ptr(), _RR_DTYPE[self.dtype], self.ntotal, self.dim, self.d, out.data_ptr(),
-                                    _stream_ptr()), "rr_centroid")
+            check(lib().rr_centroid(self._xb.data_ptr(), _calls.RR_DTYPE[self.dtype], self.ntotal, self.dim, self.d, out.data_ptr(),
+                                    _calls.stream_ptr()), "rr_centroid")
         return out[: self.d]
 
     @property
@@ -359,89 +359,29 @@ class FlatIndex(_Faithful):
         return self._xb[: self.ntotal]
 
     # -- search ------------------------------------------------------------------------------
-    def _workspace(self, k):
-        ws = self._ws.get(k)
-        if ws is None:
-            nbytes = lib().rr_flat_search_workspace_bytes_for(k, self.dim)
-            if nbytes == 0:
-                raise ValueError(f"k must be in [1, {_lib.RR_MAX_K}], got {k}")
-            self._ws = {k: torch.empty(nbytes, dtype=torch.uint8, device=self.device)}
-            ws = self._ws[k]
-        return ws
-
-    def prepare_queries(self, xq):
-        """float32 [nq,d] (numpy or tensor) -> device [nq,dim] in the index dtype (normalised for cosine).
-        exact_f32 / exact_l2: the pair (half [nq,dim], f32 [nq,d]) that search_prepared() takes."""
-        if self._faith:
-            return self._prepare_f32(xq)
-        if isinstance(xq, np.ndarray):
-            xq = torch.from_numpy(np.ascontiguousarray(xq, dtype=np.float32))
-        if xq.dim() != 2 or xq.shape[1] != self.d:
-            raise ValueError(f"queries must be [nq,{self.d}]")
-        xq = xq.to(self.device, dtype=torch.float32).contiguous()
-        out = torch.empty((xq.shape[0], self.dim), dtype=self._xb.dtype, device=self.device)
-        check(lib().rr_rows_to_half(xq.data_ptr(), xq.shape[0], self.d, self.d, out.data_ptr(), _RR_DTYPE[self.dtype],
-                                    self.dim, int(self.metric == "cosine"), _stream_ptr()), "rr_rows_to_half")
-        return out
-
     def search_prepared(self, xq_half, k, id_offset=0, out=None, route_mask=None):
         """Device-to-device search: xq_half [nq,dim] index dtype -> (D f32[nq,k], I i64[nq,k]) CUDA tensors.
         route_mask: optional bool/uint8 CUDA tensor [nq] (may be a strided column of the router's [nq,C] mask):
         queries with a zero entry get an all-padding result.  Enqueued on the current stream, no host sync.
         exact_f32 / exact_l2: xq_half is the (half, f32) pair of prepare_queries(); one host read of the proof flags."""
         if self._faith:
-            return self._faithful_search(xq_half, k, route_mask, out, self._segments(id_offset, route_mask), self.ntotal, self._mask_args)
-        if xq_half.dtype != self._xb.dtype or xq_half.dim() != 2 or xq_half.shape[1] != self.dim or not xq_half.is_contiguous():
-            raise ValueError("search_prepared() needs contiguous [nq, dim] queries of the index dtype")
-        nq = xq_half.shape[0]
-        if self._x8 is not None and nq > 0:
+            return self._faithful_search(xq_half, k, route_mask, out, self._segments(id_offset, route_mask), self.ntotal)
+        _calls.check_half_queries(xq_half, self._xb.dtype, self.dim, "search_prepared() needs contiguous [nq, dim] queries of the index dtype")
+        if self._x8 is not None and xq_half.shape[0] > 0:
             # screened search; the proof flags are the one host read of this path
             D, I, exact = self.search_screened(xq_half, k, id_offset, out, route_mask)
             if bool(exact.all()):
                 return D, I
             self.screen_fallbacks += 1
             out = (D, I)
-        ws = self._workspace(k)
-        if out is None:
-            D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-            I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        else:
-            D, I = out
-        mptr, mstride = self._mask_args(route_mask, nq)
-        if self.metric == "l2":
-            check(lib().rr_flat_search_l2(self._xb.data_ptr(), self._hn.data_ptr() if self._hn is not None else None,
-                                          _RR_DTYPE[self.dtype], self.ntotal, self.dim, xq_half.data_ptr(), nq, k, D.data_ptr(),
-                                          I.data_ptr(), id_offset, ws.data_ptr(), ws.numel(), mptr, mstride, _stream_ptr()),
-                  "rr_flat_search_l2")
-        else:
-            check(lib().rr_flat_search(self._xb.data_ptr(), _RR_DTYPE[self.dtype], self.ntotal, self.dim, xq_half.data_ptr(), nq, k,
-                                       D.data_ptr(), I.data_ptr(), id_offset, ws.data_ptr(), ws.numel(), mptr, mstride, _stream_ptr()),
-                  "rr_flat_search")
-        return D, I
-
-    def _segments(self, id_offset=0, route_mask=None):
-        return (_lib.SegmentStruct * 1)(_lib.SegmentStruct(0, self.ntotal, int(id_offset), 0 if route_mask is not None else -1, 0))
-
-    def search_exact_f32(self, xq_f32_dev, k, list_len=None, route_mask=None, id_offset=0):
-        """exact_f32 index, device to device, no host sync: float32 queries [nq,d] -> (D, I, exact, eps) CUDA tensors.  exact[q] == 1
-        where the top-k is proven on the f32 rows; eps[q] is the bound on the half-precision scan's error for query q (an exact_l2
-        index returns the bound [nq, 2] = (A(q), R(q)) in its place).  search() and search_prepared() wrap this with the retry
-        and the exact fallback."""
-        if not self._faith:
-            raise _lib.RagrouteHipError("search_exact_f32() needs an index built with exact_f32=True or exact_l2=True")
-        xh, xf = self._prepare_f32(xq_f32_dev)
-        L = self._faithful_list_len(k) if list_len is None else int(list_len)
-        mptr, mstride = self._mask_args(route_mask, xh.shape[0])
-        return self._faithful_raw(xh, xf, int(k), L, self._segments(id_offset, route_mask), self.ntotal, mptr, mstride)
+        return self._half_search(xq_half, k, route_mask, out, self.ntotal, id_offset)
 
     def search(self, xq, k):
         """faiss call shape: float32 [nq,d] -> (D float32[nq,k], I int64[nq,k]) numpy arrays."""
-        with torch.cuda.device(self.device):
-            D, I = self.search_prepared(self.prepare_queries(xq), int(k))
-            return D.cpu().numpy(), I.cpu().numpy()
+        return super().search(xq, k)
 
 
-class SegmentedIndex(_Faithful):
+class SegmentedIndex(_Index):
     """Several data sources that are searched with the SAME query embeddings, resident in ONE HBM matrix and searched in ONE
     pass (C ABI `rr_flat_search_segments`): MedRAG's four sources all use MedCPT, five FeB4RAG sources UAE-Large-V1
     (reference ragroute/config.py:37-71).  The reference asks every selected source separately (`index.search`,
@@ -459,17 +399,10 @@ class SegmentedIndex(_Faithful):
 
     def __init__(self, d, rows_per_source, id_offsets=None, mask_cols=None, metric="ip", dtype="fp16", device=None, exact_f32=False,
                  exact_l2=False):
-        if metric not in ("ip", "cosine", "l2"):
-            raise ValueError(f"unknown metric {metric!r}")
-        if exact_f32 and metric == "l2":
-            raise ValueError("exact_f32 serves the ip / cosine metrics only")
-        if exact_l2 and metric != "l2":
-            raise ValueError("exact_l2 serves the l2 metric only (ip / cosine: exact_f32)")
         rows = [int(n) for n in rows_per_source]
         if not 1 <= len(rows) <= _lib.RR_MAX_SEGMENTS or min(rows) < 0:
             raise ValueError(f"need 1 .. {_lib.RR_MAX_SEGMENTS} sources with >= 0 rows each")
-        self._proto = FlatIndex(d, metric=metric, dtype=dtype, device=device, exact_f32=exact_f32, exact_l2=exact_l2)   # query conversion, workspace, dims
-        self.d, self.dim, self.metric, self.dtype, self.device = self._proto.d, self._proto.dim, metric, dtype, self._proto.device
+        super().__init__(d, metric, dtype, device, exact_f32, exact_l2)
         self.rows = rows
         self.id_offsets = [int(v) for v in (id_offsets if id_offsets is not None else [s << 40 for s in range(len(rows))])]
         self.mask_cols = [int(v) for v in (mask_cols if mask_cols is not None else range(len(rows)))]
@@ -483,17 +416,30 @@ class SegmentedIndex(_Faithful):
         self.n_rows_total = self.begins[-1] + rows[-1]            # nothing behind the last valid row is ever read
         if self.n_rows_total > 0xFFFFFFE0:
             raise ValueError("more than 2^32 - 32 rows in one segmented matrix")
-        self._xb = torch.zeros((max(1, self.n_rows_total), self.dim), dtype=_TORCH_DTYPE[dtype], device=self.device)
+        self._xb = torch.zeros((max(1, self.n_rows_total), self.dim), dtype=_calls.TORCH_DTYPE[dtype], device=self.device)
         self._segs = (_lib.SegmentStruct * len(rows))(*[_lib.SegmentStruct(b, n, o, c, 0)
                                                         for b, n, o, c in zip(self.begins, rows, self.id_offsets, self.mask_cols)])
         self.ntotal = sum(rows)
-        # metric "l2": |x|^2 / 2 of every matrix row, aligned with _xb (alignment gaps: unspecified, never used)
-        self._hn = torch.zeros(max(1, self.n_rows_total), dtype=torch.float32, device=self.device) if metric == "l2" else None
-        self.exact_f32 = bool(exact_f32)
-        self.exact_l2 = bool(exact_l2)
-        if self._faith:
-            self._faithful_init(self.n_rows_total)
+        if metric == "l2":   # aligned with _xb (alignment gaps: unspecified, never used)
+            self._hn = torch.zeros(max(1, self.n_rows_total), dtype=torch.float32, device=self.device)
+        self._faithful_init(self.n_rows_total)
 
+    @property
+    def _n_rows(self):
+        return self.n_rows_total
+
+    def _segments(self, id_offset=0, route_mask=None):
+        return self._segs
+
+    def _mask_args(self, route_mask, nq):
+        if route_mask is None:
+            return None, 0
+        if (route_mask.dtype not in (torch.bool, torch.uint8) or route_mask.dim() != 2 or route_mask.shape[0] != nq
+                or not route_mask.is_cuda or route_mask.stride(1) != 1 or route_mask.shape[1] <= max(self.mask_cols)):
+            raise ValueError("route_mask must be a bool/uint8 CUDA matrix [nq, C] with unit column stride covering every mask column")
+        return route_mask.data_ptr(), route_mask.stride(0)
+
+    # -- storage -----------------------------------------------------------------------------
     def rows_of(self, s):
         """Device view [n_s, dim] of source s (fill it with rows in the index dtype, zero padded to dim)."""
         return self._xb[self.begins[s]: self.begins[s] + self.rows[s]]
@@ -508,8 +454,7 @@ class SegmentedIndex(_Faithful):
         if self.metric != "l2" or self.rows[s] == 0:
             return
         with torch.cuda.device(self.device):
-            check(lib().rr_half_sqnorms(self.rows_of(s).data_ptr(), _RR_DTYPE[self.dtype], self.rows[s], self.dim,
-                                        self.norms_of(s).data_ptr(), _stream_ptr()), "rr_half_sqnorms")
+            _calls.half_sqnorms(self.rows_of(s), self.rows[s], self.norms_of(s))
 
     def _point_at(self, idx, s):
         """Make FlatIndex idx a view of source s: its rows and, for "l2", its slice of the norms (nothing is recomputed)."""
@@ -526,21 +471,9 @@ class SegmentedIndex(_Faithful):
         """Ingest float32 rows [n_s, d] (numpy or tensor) into source s (normalised for cosine)."""
         if x.shape[0] != self.rows[s] or x.shape[1] != self.d:
             raise ValueError(f"source {s} holds [{self.rows[s]}, {self.d}] rows")
-        out = self.rows_of(s)
-        if self._faith:
-            with torch.cuda.device(self.device):
-                self._ingest_f32(x, self._xf[self.begins[s]: self.begins[s] + self.rows[s]], out, chunk_rows)
-                self._faithful_build(self.n_rows_total)
-            self.refresh_norms(s)
-            return
         with torch.cuda.device(self.device):
-            for b in range(0, x.shape[0], chunk_rows):
-                part = x[b: b + chunk_rows]
-                if isinstance(part, np.ndarray):
-                    part = torch.from_numpy(np.ascontiguousarray(part, dtype=np.float32))
-                part = part.to(self.device, dtype=torch.float32).contiguous()
-                check(lib().rr_rows_to_half(part.data_ptr(), part.shape[0], self.d, self.d, out[b: b + part.shape[0]].data_ptr(),
-                                            _RR_DTYPE[self.dtype], self.dim, int(self.metric == "cosine"), _stream_ptr()), "rr_rows_to_half")
+            self._ingest(x, self.begins[s], chunk_rows)
+            self._faithful_build()
         self.refresh_norms(s)
 
     @classmethod
@@ -561,57 +494,16 @@ class SegmentedIndex(_Faithful):
             seg._point_at(i, s)
         return seg
 
-    def prepare_queries(self, xq):
-        return self._proto.prepare_queries(xq)
-
+    # -- search ------------------------------------------------------------------------------
     def search_prepared(self, xq_half, k, route_mask=None, out=None):
         """xq_half [nq, dim] index dtype -> (D f32 [nq,k], I i64 [nq,k]) CUDA tensors: the merged top-k over the selected sources.
         route_mask: optional bool/uint8 CUDA matrix [nq, C] (the router's mask; source s reads column mask_cols[s]).
         exact_f32 / exact_l2: xq_half is the (half, f32) pair of prepare_queries()."""
         if self._faith:
-            return self._faithful_search(xq_half, k, route_mask, out, self._segs, self.n_rows_total, self._mask_args)
-        if xq_half.dtype != self._xb.dtype or xq_half.dim() != 2 or xq_half.shape[1] != self.dim or not xq_half.is_contiguous():
-            raise ValueError("search_prepared() needs contiguous [nq, dim] queries of the index dtype")
-        nq = xq_half.shape[0]
-        ws = self._proto._workspace(k)
-        if out is None:
-            D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-            I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        else:
-            D, I = out
-        mptr, mstride = self._mask_args(route_mask, nq)
-        if self.metric == "l2":
-            check(lib().rr_flat_search_segments_l2(self._xb.data_ptr(), self._hn.data_ptr(), _RR_DTYPE[self.dtype], self.n_rows_total,
-                                                   self.dim, self._segs, len(self.rows), xq_half.data_ptr(), nq, k, D.data_ptr(),
-                                                   I.data_ptr(), ws.data_ptr(), ws.numel(), mptr, mstride, _stream_ptr()),
-                  "rr_flat_search_segments_l2")
-            return D, I
-        check(lib().rr_flat_search_segments(self._xb.data_ptr(), _RR_DTYPE[self.dtype], self.n_rows_total, self.dim, self._segs,
-                                            len(self.rows), xq_half.data_ptr(), nq, k, D.data_ptr(), I.data_ptr(), ws.data_ptr(),
-                                            ws.numel(), mptr, mstride, _stream_ptr()), "rr_flat_search_segments")
-        return D, I
-
-    def _mask_args(self, route_mask, nq):
-        if route_mask is None:
-            return None, 0
-        if (route_mask.dtype not in (torch.bool, torch.uint8) or route_mask.dim() != 2 or route_mask.shape[0] != nq
-                or not route_mask.is_cuda or route_mask.stride(1) != 1 or route_mask.shape[1] <= max(self.mask_cols)):
-            raise ValueError("route_mask must be a bool/uint8 CUDA matrix [nq, C] with unit column stride covering every mask column")
-        return route_mask.data_ptr(), route_mask.stride(0)
+            return self._faithful_search(xq_half, k, route_mask, out, self._segs, self.n_rows_total)
+        _calls.check_half_queries(xq_half, self._xb.dtype, self.dim, "search_prepared() needs contiguous [nq, dim] queries of the index dtype")
+        return self._half_search(xq_half, k, route_mask, out, self.n_rows_total, segs=self._segs)
 
     def search_exact_f32(self, xq_f32_dev, k, list_len=None, route_mask=None):
         """As FlatIndex.search_exact_f32, over the segments (route_mask [nq, C] as search_prepared)."""
-        if not self._faith:
-            raise _lib.RagrouteHipError("search_exact_f32() needs an index built with exact_f32=True or exact_l2=True")
-        xh, xf = self._prepare_f32(xq_f32_dev)
-        L = self._faithful_list_len(k) if list_len is None else int(list_len)
-        mptr, mstride = self._mask_args(route_mask, xh.shape[0])
-        return self._faithful_raw(xh, xf, int(k), L, self._segs, self.n_rows_total, mptr, mstride)
-
-    def search(self, xq, k, route_mask=None):
-        """float32 [nq,d] -> (D, I) numpy arrays (merged over the selected sources)."""
-        with torch.cuda.device(self.device):
-            if route_mask is not None and not isinstance(route_mask, torch.Tensor):
-                route_mask = torch.from_numpy(np.ascontiguousarray(route_mask, dtype=np.uint8)).to(self.device)
-            D, I = self.search_prepared(self.prepare_queries(xq), int(k), route_mask)
-            return D.cpu().numpy(), I.cpu().numpy()
+        return super().search_exact_f32(xq_f32_dev, k, list_len, route_mask)

@@ -11,7 +11,28 @@ Everything is enqueued on the current stream; nothing synchronises with the host
 
 The reference's counterpart is the fan-out / gather / concat / rerank of http_server.py:198-209, 227-257, 280-293: one
 message per selected source, replies collected in arrival order, flat candidate lists merged by score."""
+from typing import NamedTuple
+
 from .sharded import SHARD_SHIFT, alloc_gathered, alloc_packed, exchange_packed, max_over_ranks, merge_gathered
+
+
+class SearchUnit(NamedTuple):
+    """What one scan call serves and one exchange slot carries.  kind "shard": a FlatIndex over source sids[0], or over a row slice
+    of it (placement.py), whose ids start at id_offset; kind "segments": a SegmentedIndex over the sources sids, which holds the id
+    offsets itself (id_offset None)."""
+    kind: str
+    index: object
+    sids: list
+    id_offset: int | None
+
+    @classmethod
+    def of(cls, index, sids, id_offset=None):
+        """The unit of an index and its source ids; a shard's ids start at sids[0] << 40 unless id_offset says otherwise."""
+        from .flat_index import SegmentedIndex
+        sids = [int(s) for s in sids]
+        if isinstance(index, SegmentedIndex):
+            return cls("segments", index, sids, None)
+        return cls("shard", index, sids, sids[0] << SHARD_SHIFT if id_offset is None else int(id_offset))
 
 
 class RetrievalPipeline:
@@ -39,37 +60,28 @@ class RetrievalPipeline:
         self.group = group
         self.slots = slots
         self._packed = {}
-        # units: what one scan call serves and one exchange slot carries: ("shard", FlatIndex, [sid]) or ("segments", SegmentedIndex, [sids])
-        # a "shard" unit may be a row slice of its source (placement.py): its ids start at (sid << 40) + row_begin
-        self.units = []
         if units is not None:
-            from .flat_index import SegmentedIndex
-            for u in units:
-                obj, sids = u[0], [int(s) for s in u[1]]
-                seg = isinstance(obj, SegmentedIndex)
-                self.units.append(("segments" if seg else "shard", obj, sids, None if seg else int(u[2]) if len(u) > 2 else sids[0] << SHARD_SHIFT))
+            self.units = [SearchUnit.of(*u) for u in units]
         elif share_queries is None:
-            self.units = [("shard", idx, [sid], sid << SHARD_SHIFT) for idx, sid in zip(self.shards, self.shard_ids)]
+            self.units = [SearchUnit.of(idx, [sid]) for idx, sid in zip(self.shards, self.shard_ids)]
         else:
             if len(share_queries) != len(self.shards):
                 raise ValueError("one share_queries key per shard")
             from .flat_index import SegmentedIndex
-            groups = {}
+            self.units, groups = [], {}
             for idx, sid, key in zip(self.shards, self.shard_ids, share_queries):
                 if getattr(idx, "metric", None) in ("ip", "cosine", "l2"):
                     groups.setdefault((key, idx.d, idx.metric, idx.dtype), []).append((sid, idx))
                 else:
-                    self.units.append(("shard", idx, [sid], sid << SHARD_SHIFT))
+                    self.units.append(SearchUnit.of(idx, [sid]))
             for members in groups.values():
                 members.sort(key=lambda m: m[0])      # ascending source id = ascending id offset: ties by ascending global id
-                if len(members) == 1:
-                    self.units.append(("shard", members[0][1], [members[0][0]], members[0][0] << SHARD_SHIFT))
-                else:
-                    sids = [m[0] for m in members]
-                    seg = SegmentedIndex.from_indexes([m[1] for m in members], id_offsets=[s << SHARD_SHIFT for s in sids], mask_cols=sids)
-                    self.units.append(("segments", seg, sids, None))
-            self.units.sort(key=lambda u: u[2][0])
-        l2 = {getattr(u[1], "metric", "ip") == "l2" for u in self.units}
+                sids = [m[0] for m in members]
+                idx = members[0][1] if len(members) == 1 else SegmentedIndex.from_indexes(
+                    [m[1] for m in members], id_offsets=[s << SHARD_SHIFT for s in sids], mask_cols=sids)
+                self.units.append(SearchUnit.of(idx, sids))
+            self.units.sort(key=lambda u: u.sids[0])
+        l2 = {getattr(u.index, "metric", "ip") == "l2" for u in self.units}
         if len(l2) > 1:
             raise ValueError("a pipeline's units must all be \"l2\" or all ip / cosine: distances and scores cannot be merged")
         self.descending = l2 != {True}     # the merge direction and the padding of the exchange slots follow the units' metric
@@ -85,7 +97,7 @@ class RetrievalPipeline:
             storage dtype, zero padded (synthetic corpora generated in place: nothing is held twice).
         Exchange slots = placement.slots on every rank (known from the plan: no collective at set-up)."""
         import torch
-        from .flat_index import _TORCH_DTYPE, FlatIndex, SegmentedIndex
+        from .flat_index import FlatIndex, SegmentedIndex
         from ._lib import RR_MAX_SEGMENTS
         if (rows_f32 is None) == (fill_half is None):
             raise ValueError("give exactly one of rows_f32 / fill_half")
@@ -99,7 +111,7 @@ class RetrievalPipeline:
                     sl = slices[0]
                     idx = FlatIndex(src0.dim, metric=src0.metric, dtype=src0.dtype, device=dev)
                     if fill_half is not None:
-                        xb = torch.zeros((max(1, sl.n_rows), idx.dim), dtype=_TORCH_DTYPE[src0.dtype], device=dev)
+                        xb = torch.zeros((max(1, sl.n_rows), idx.dim), dtype=idx.xb.dtype, device=dev)
                         fill_half(placement.sources[sl.sid], sl, xb[: sl.n_rows])
                         idx.adopt(xb, ntotal=sl.n_rows)
                     elif sl.n_rows:
@@ -180,7 +192,7 @@ class RetrievalPipeline:
             import torch
             e_start = torch.cuda.Event(enable_timing=True)
             e_start.record()
-        for slot, (kind, idx, sids, id_offset) in enumerate(self.units):
+        for slot, (kind, idx, sids, id_offset) in enumerate(self.units):   # (unpacked: `units` may be assigned plain tuples of these fields)
             q = xq[sids[0]] if per_shard else xq          # (a group shares one encoder: any member's embedding)
             if kind == "segments":
                 idx.search_prepared(idx.prepare_queries(q), k, route_mask=mask, out=(D[slot], I[slot]))

@@ -12,58 +12,41 @@
     ragroute::router_mlp(xq, folded weights..., b3, prob_threshold) -> (logits, mask)       router.py:241-283, 50-55
 
 All take and return CUDA tensors, enqueue on the current stream and never synchronise.  The faiss-shaped classes in
-flat_index.py are thin conveniences over the same entry points (they additionally cache the workspace)."""
+flat_index.py are conveniences over the same entry points, reached through the same call layer (_calls.py); each of them caches
+a workspace of its own, the ops share the one below."""
 import torch
 
+from . import _calls
 from . import _lib
 from ._lib import check, lib
 
 _WS = {}
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+_K_RANGE = f"k must be in [1, {_lib.RR_MAX_K}]"
 
 
 def _workspace(device, k):
-    key = (device.index, k)
-    ws = _WS.get(key)
-    if ws is None:
-        nbytes = lib().rr_flat_search_workspace_bytes(k)
-        if nbytes == 0:
-            raise ValueError(f"k must be in [1, {_lib.RR_MAX_K}]")
-        _WS.clear()
-        ws = _WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    return ws
+    return _calls.workspace(_WS, (device.index, k), device, _K_RANGE, "rr_flat_search_workspace_bytes", k)
 
 
-def _dtype_code(t):
-    if t.dtype == torch.float16:
-        return _lib.RR_DTYPE_F16
-    if t.dtype == torch.bfloat16:
-        return _lib.RR_DTYPE_BF16
-    raise ValueError("corpus / queries must be float16 or bfloat16")
+def _corpus_and_queries(op, xb, xq):
+    """The half corpus matrix and the prepared queries of `op`, both contiguous."""
+    message = f"{op}: xb [n,dim] and xq [nq,dim] must be CUDA tensors of the same half dtype and padded width"
+    if not (xb.is_cuda and xq.is_cuda and xb.dim() == 2):
+        raise ValueError(message)
+    xb, xq = xb.contiguous(), xq.contiguous()
+    _calls.check_half_queries(xq, xb.dtype, xb.shape[1], message)
+    return xb, xq
 
 
 @torch.library.custom_op("ragroute::flat_topk", mutates_args=())
 def flat_topk(xb: torch.Tensor, xq: torch.Tensor, k: int, id_offset: int = 0, l2: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
-    if not (xb.is_cuda and xq.is_cuda and xb.dim() == 2 and xq.dim() == 2 and xb.shape[1] == xq.shape[1] and xb.dtype == xq.dtype):
-        raise ValueError("flat_topk: xb [n,dim] and xq [nq,dim] must be CUDA tensors of the same half dtype and padded width")
-    xb, xq = xb.contiguous(), xq.contiguous()
-    n, dim = xb.shape
-    nq = xq.shape[0]
-    D = torch.empty((nq, k), dtype=torch.float32, device=xb.device)
-    I = torch.empty((nq, k), dtype=torch.int64, device=xb.device)
+    xb, xq = _corpus_and_queries("flat_topk", xb, xq)
+    n = xb.shape[0]
+    D, I = _calls.out_pair(xq.shape[0], k, xb.device)
     ws = _workspace(xb.device, k)
     with torch.cuda.device(xb.device):
-        if l2:
-            hn = torch.empty(max(1, n), dtype=torch.float32, device=xb.device)
-            check(lib().rr_half_sqnorms(xb.data_ptr(), _dtype_code(xb), n, dim, hn.data_ptr(), _stream()), "rr_half_sqnorms")
-            check(lib().rr_flat_search_l2(xb.data_ptr(), hn.data_ptr(), _dtype_code(xb), n, dim, xq.data_ptr(), nq, k, D.data_ptr(),
-                                          I.data_ptr(), id_offset, ws.data_ptr(), ws.numel(), None, 0, _stream()), "rr_flat_search_l2")
-        else:
-            check(lib().rr_flat_search(xb.data_ptr(), _dtype_code(xb), n, dim, xq.data_ptr(), nq, k, D.data_ptr(), I.data_ptr(),
-                                       id_offset, ws.data_ptr(), ws.numel(), None, 0, _stream()), "rr_flat_search")
+        hn = _calls.half_sqnorms(xb, n) if l2 else None
+        _calls.half_search(xb, n, xq, k, D, I, ws, None, 0, id_offset=id_offset, l2=l2, hn=hn)
     return D, I
 
 
@@ -83,14 +66,11 @@ def flat_topk_segments(xb: torch.Tensor, row_begins: list[int], rows: list[int],
     n_seg = len(rows)
     if not (len(row_begins) == len(id_offsets) == len(mask_cols) == n_seg and 1 <= n_seg <= _lib.RR_MAX_SEGMENTS):
         raise ValueError("flat_topk_segments: one begin / row count / id offset / mask column per segment (1 .. 32 segments)")
-    if not (xb.is_cuda and xq.is_cuda and xb.dim() == 2 and xq.dim() == 2 and xb.shape[1] == xq.shape[1] and xb.dtype == xq.dtype):
-        raise ValueError("flat_topk_segments: xb [n,dim] and xq [nq,dim] must be CUDA tensors of the same half dtype and padded width")
-    xb, xq = xb.contiguous(), xq.contiguous()
-    nq = xq.shape[0]
+    xb, xq = _corpus_and_queries("flat_topk_segments", xb, xq)
+    nq, n = xq.shape[0], xb.shape[0]
     segs = (_lib.SegmentStruct * n_seg)(*[_lib.SegmentStruct(int(b), int(r), int(o), int(c), 0)
                                           for b, r, o, c in zip(row_begins, rows, id_offsets, mask_cols)])
-    D = torch.empty((nq, k), dtype=torch.float32, device=xb.device)
-    I = torch.empty((nq, k), dtype=torch.int64, device=xb.device)
+    D, I = _calls.out_pair(nq, k, xb.device)
     ws = _workspace(xb.device, k)
     mptr, mstride = None, 0
     if route_mask is not None:
@@ -102,20 +82,12 @@ def flat_topk_segments(xb: torch.Tensor, row_begins: list[int], rows: list[int],
         raise ValueError("flat_topk_segments: half_sqnorm belongs to l2=True")
     with torch.cuda.device(xb.device):
         if l2:
-            n = xb.shape[0]
             if half_sqnorm is None:
-                half_sqnorm = torch.empty(max(1, n), dtype=torch.float32, device=xb.device)
-                check(lib().rr_half_sqnorms(xb.data_ptr(), _dtype_code(xb), n, xb.shape[1], half_sqnorm.data_ptr(), _stream()), "rr_half_sqnorms")
+                half_sqnorm = _calls.half_sqnorms(xb, n)
             elif not (half_sqnorm.is_cuda and half_sqnorm.dtype == torch.float32 and half_sqnorm.dim() == 1 and half_sqnorm.shape[0] >= n):
                 raise ValueError("flat_topk_segments: half_sqnorm must be a float32 CUDA vector with one entry per matrix row")
             half_sqnorm = half_sqnorm.contiguous()
-            check(lib().rr_flat_search_segments_l2(xb.data_ptr(), half_sqnorm.data_ptr(), _dtype_code(xb), n, xb.shape[1], segs, n_seg,
-                                                   xq.data_ptr(), nq, k, D.data_ptr(), I.data_ptr(), ws.data_ptr(), ws.numel(), mptr, mstride,
-                                                   _stream()), "rr_flat_search_segments_l2")
-            return D, I
-        check(lib().rr_flat_search_segments(xb.data_ptr(), _dtype_code(xb), xb.shape[0], xb.shape[1], segs, n_seg, xq.data_ptr(), nq, k,
-                                            D.data_ptr(), I.data_ptr(), ws.data_ptr(), ws.numel(), mptr, mstride, _stream()),
-              "rr_flat_search_segments")
+        _calls.half_search(xb, n, xq, k, D, I, ws, mptr, mstride, segs=segs, l2=l2, hn=half_sqnorm)
     return D, I
 
 
@@ -129,7 +101,7 @@ def l2_normalize_(x: torch.Tensor) -> None:
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()):
         raise ValueError("l2_normalize_: contiguous float32 CUDA matrix expected")
     with torch.cuda.device(x.device):
-        check(lib().rr_l2_normalize_f32(x.data_ptr(), x.shape[0], x.shape[1], _stream()), "rr_l2_normalize_f32")
+        _calls.l2_normalize_(x)
 
 
 @torch.library.custom_op("ragroute::merge_topk", mutates_args=())
@@ -159,12 +131,8 @@ def _(buf, slots, nq, k_in, k, descending=True):
 def rows_to_half(x: torch.Tensor, dim: int, bf16: bool = False, normalize: bool = False) -> torch.Tensor:
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2):
         raise ValueError("rows_to_half: float32 CUDA matrix expected")
-    x = x.contiguous()
-    out = torch.empty((x.shape[0], dim), dtype=torch.bfloat16 if bf16 else torch.float16, device=x.device)
     with torch.cuda.device(x.device):
-        check(lib().rr_rows_to_half(x.data_ptr(), x.shape[0], x.shape[1], x.shape[1], out.data_ptr(),
-                                    _lib.RR_DTYPE_BF16 if bf16 else _lib.RR_DTYPE_F16, dim, int(normalize), _stream()), "rr_rows_to_half")
-    return out
+        return _calls.rows_to_half(x.contiguous(), dim, torch.bfloat16 if bf16 else torch.float16, normalize)
 
 
 @rows_to_half.register_fake
@@ -196,7 +164,7 @@ def router_mlp(xq: torch.Tensor, w1q: torch.Tensor, c1: torch.Tensor, ln1_g: tor
     logits = torch.empty((nq, C), dtype=torch.float32, device=xq.device)
     mask = torch.empty((nq, C), dtype=torch.uint8, device=xq.device)
     with torch.cuda.device(xq.device):
-        check(lib().rr_router_mlp(ctypes.byref(st), xq.data_ptr(), nq, logits.data_ptr(), mask.data_ptr(), _stream()), "rr_router_mlp")
+        check(lib().rr_router_mlp(ctypes.byref(st), xq.data_ptr(), nq, logits.data_ptr(), mask.data_ptr(), _calls.stream_ptr()), "rr_router_mlp")
     return logits, mask.view(torch.bool)
 
 

@@ -14,7 +14,7 @@ import sys
 
 import torch
 
-from ragroute_amd._lib import check, lib
+from ragroute_amd._calls import half_search
 from ragroute_amd.flat_index import FlatIndex
 
 SHAPES = {  # name: rows, d, queries, k, corpus
@@ -70,14 +70,7 @@ def measure(name, iters, metric="ip"):
     IL = torch.empty((nq, L), dtype=torch.int64, device=dev)
 
     def scan_only():
-        if l2:
-            check(lib().rr_flat_search_segments_l2(idx._xb.data_ptr(), idx._hn.data_ptr(), 0, idx.ntotal, idx.dim, seg, 1, prep[0].data_ptr(), nq,
-                                                   L, DL.data_ptr(), IL.data_ptr(), ws.data_ptr(), ws.numel(), None, 0,
-                                                   torch.cuda.current_stream().cuda_stream), "rr_flat_search_segments_l2")
-            return
-        check(lib().rr_flat_search_segments(idx._xb.data_ptr(), 0, idx.ntotal, idx.dim, seg, 1, prep[0].data_ptr(), nq, L, DL.data_ptr(),
-                                            IL.data_ptr(), ws.data_ptr(), ws.numel(), None, 0, torch.cuda.current_stream().cuda_stream),
-              "rr_flat_search_segments")
+        half_search(idx._xb, idx.ntotal, prep[0], L, DL, IL, ws, None, 0, segs=seg, l2=l2, hn=idx._hn)
     t_plain = timed(lambda: plain.search_prepared(prep[0], k), iters)
     t_scan = timed(scan_only, iters)
     t_raw = timed(lambda: idx._faithful_raw(prep[0], prep[1], k, L, seg, idx.ntotal, None, 0), iters)
