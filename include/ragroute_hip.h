@@ -287,10 +287,17 @@ int rr_merge_topk_gathered(const void* d_gathered, int n_ranks, size_t rank_stri
 /* Router MLP (CorpusRoutingNN) with the feature build and StandardScaler folded into fc1.
  * Replaces, for a batch of queries, reference ragroute/router.py:241-283
  * (select_relevant_sources_ragroute: pad/concat features, scaler.transform, model forward,
- * sigmoid, threshold) and router.py:50-55 (CorpusRoutingNN.forward).  All pointers device f32. */
+ * sigmoid, threshold) and router.py:50-55 (CorpusRoutingNN.forward).  All pointers device f32.
+ *   logit(q, c) = w3 . relu(LN128(W2 relu(LN256(W1q' q_model(c) + c1[c])) + b2)) + b3, LN = LayerNorm with the biased variance
+ *   and ln_eps inside the square root, all in f32.  A NaN in one embedding of a query makes the logits of that query's sources on
+ *   that model NaN (mask 0) and changes no other output.
+ * d_max is 1 ... 8191: the widest embedding every batch size can be served at (4 queries of d_max floats share the 160 KiB of a
+ * workgroup's LDS with 32 KiB of partial sums in the small-batch kernel); a header outside that range is RR_ERR_INVALID in
+ * rr_router_mlp and rr_router_mlp_ws, and rr_router_workspace_bytes returns 0 for it, before any device call.
+ * model_of_source need not be sorted, and n_models may exceed the models it names (the embedding of an unused model is ignored). */
 typedef struct rr_router_weights {
   int32_t n_sources;               /* C: rows per query */
-  int32_t d_max;                   /* padded query-embedding length (config.py:92-96) */
+  int32_t d_max;                   /* padded query-embedding length (config.py:92-96), 1 ... 8191 */
   int32_t n_models;                /* distinct query-embedding models M */
   int32_t reserved;
   const int32_t* model_of_source;  /* [C] which of the M embeddings source c uses */

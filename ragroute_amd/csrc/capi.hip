@@ -745,12 +745,13 @@ int rr_merge_topk_gathered(const void* gathered, int n_ranks, size_t rank_stride
 }
 
 static bool router_header_ok(const rr_router_weights* w) {
-  return w && w->n_sources >= 1 && w->d_max >= 1 && w->n_models >= 1 && w->d_max <= 8448;
+  // d_max: the widest embedding EVERY batch size can be served at (the small-batch kernel's LDS, rr_kernels.h)
+  return w && w->n_sources >= 1 && w->d_max >= 1 && w->n_models >= 1 && w->d_max <= rr::kRouterMaxDmax;
 }
 // Argument validation of the router entry points; `who` names the entry point in the messages.  nq == 0 needs no buffers.
 static int router_check(const rr_router_weights* w, const float* xq, int nq, float* logits, uint8_t* mask, const char* who) {
   if (!w || nq < 0) return fail(RR_ERR_INVALID, "%s: bad arguments", who);
-  if (!router_header_ok(w)) return fail(RR_ERR_INVALID, "%s: bad weight header", who);
+  if (!router_header_ok(w)) return fail(RR_ERR_INVALID, "%s: bad weight header (n_sources, n_models >= 1, d_max 1 ... 8191)", who);
   if (nq > 0 && (!xq || !logits || !mask || !w->w1q || !w->c1 || !w->w2 || !w->w3 || !w->model_of_source))
     return fail(RR_ERR_INVALID, "%s: null pointer", who);
   return RR_OK;

@@ -43,7 +43,8 @@ __global__ __launch_bounds__(1024) void router_mlp_kernel(rr_router_weights w, c
     const int q = q0 + t;
     const float v = q < nq ? xq[((size_t)q * w.n_models + m) * dmax + k] : 0.f;
     xs[i] = v;
-    if (v != 0.f) last = k + 1;   // (NaN != 0 is true: a NaN input still reaches fc1)
+    if (v != 0.f) last = max(last, k + 1);   // max: from 4 * dmax > 1024 on a thread visits several (t, k), k not ascending
+                                             // (NaN != 0 is true: a NaN input still reaches fc1)
   }
   if (last) atomicMax(&k_end_s, last);
   __syncthreads();
@@ -112,7 +113,10 @@ __global__ __launch_bounds__(1024) void router_mlp_kernel(rr_router_weights w, c
     const float rstd2 = 1.0f / sqrtf(wsum(a0 * a0 + a1 * a1) * (1.f / 128.f) + w.ln_eps);
     const float h0 = fmaxf(a0 * rstd2 * w.ln2_g[lane] + w.ln2_b[lane], 0.f);
     const float h1 = fmaxf(a1 * rstd2 * w.ln2_g[lane + 64] + w.ln2_b[lane + 64], 0.f);
-    const float logit = wsum(h0 * w.w3[lane] + h1 * w.w3[lane + 64]) + w.b3;
+    float logit = wsum(h0 * w.w3[lane] + h1 * w.w3[lane + 64]) + w.b3;
+    // A NaN or infinity in fc1 or fc2 makes that layer's rstd NaN, but fmaxf(NaN, 0) = 0 would turn the row into zeros and the
+    // logit into a finite number: the row's logit is NaN, as torch's ReLU has it (mask 0: NaN > threshold is false)
+    if (rstd != rstd || rstd2 != rstd2) logit = __builtin_nanf("");
     if (lane == 0) {
       logits[(size_t)q * w.n_sources + c] = logit;
       const float p = 1.0f / (1.0f + expf(-logit));
@@ -235,6 +239,7 @@ __global__ __launch_bounds__(256) void router_head_kernel(rr_router_weights w, i
                                                           uint8_t* __restrict__ mask) {
   __shared__ float h1[kHeadRows][256 + 1];
   __shared__ float z[kHeadRows][128 + 1];
+  __shared__ int bad[kHeadRows];   // fc1 of the row held a NaN or an infinity (its rstd is NaN): see router_mlp_kernel
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int q0 = blockIdx.x * kHeadRows, c = blockIdx.y;
   const int m = w.model_of_source[c];
@@ -277,6 +282,7 @@ __global__ __launch_bounds__(256) void router_head_kernel(rr_router_weights w, i
 #pragma unroll
       for (int i = 0; i < 4; ++i) { v[r][i] -= mean; sq += v[r][i] * v[r][i]; }
       const float rstd = 1.0f / sqrtf(wsum(sq) * (1.f / 256.f) + w.ln_eps);
+      if (lane == 0) bad[wave * 8 + r] = rstd != rstd;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int j = lane + 64 * i;
@@ -324,7 +330,8 @@ __global__ __launch_bounds__(256) void router_head_kernel(rr_router_weights w, i
     const float rstd2 = 1.0f / sqrtf(wsum(a0 * a0 + a1 * a1) * (1.f / 128.f) + w.ln_eps);
     const float g0 = fmaxf(a0 * rstd2 * w.ln2_g[lane] + w.ln2_b[lane], 0.f);
     const float g1 = fmaxf(a1 * rstd2 * w.ln2_g[lane + 64] + w.ln2_b[lane + 64], 0.f);
-    const float logit = wsum(g0 * w.w3[lane] + g1 * w.w3[lane + 64]) + w.b3;
+    float logit = wsum(g0 * w.w3[lane] + g1 * w.w3[lane + 64]) + w.b3;
+    if (bad[r] || rstd2 != rstd2) logit = __builtin_nanf("");
     if (lane == 0) {
       logits[(size_t)q * w.n_sources + c] = logit;
       const float p = 1.0f / (1.0f + expf(-logit));
@@ -363,7 +370,7 @@ hipError_t launch_router_mlp_ws(const rr_router_weights* w, const float* xq, int
 hipError_t launch_router_mlp(const rr_router_weights* w, const float* xq, int nq, float* logits, uint8_t* mask,
                              hipStream_t st) {
   if (nq == 0) return hipSuccess;
-  const size_t lds = (size_t)(4 * w->d_max + 16 * 256 + 16 * 256) * sizeof(float);
+  const size_t lds = router_mlp_lds_bytes(w->d_max);   // fits for every accepted header: d_max <= kRouterMaxDmax
   hipError_t e = hipFuncSetAttribute((const void*)router_mlp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(router_mlp_kernel, dim3((nq + 3) / 4, w->n_models), dim3(1024), lds, st, *w, xq, nq, logits, mask);

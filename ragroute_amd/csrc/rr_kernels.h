@@ -151,6 +151,17 @@ hipError_t launch_faithful_emit(bool l2, const float* Din, const int64_t* Iin, c
 // router.hip
 hipError_t launch_router_mlp(const rr_router_weights* w, const float* xq, int nq, float* logits, uint8_t* mask,
                              hipStream_t st);
+// LDS of router_mlp_kernel: the dynamic part launch_router_mlp asks for (the 4 queries' embeddings, the fc1 partials of the four
+// k-quarters, one h1 row per wave) and the kernel's static part (k_end_s, padded to 16 bytes in the gfx950 code object).  The widest
+// header the router entry points accept is the widest one this kernel - the only form for batches below 32 queries - can be launched
+// at: a workgroup has 160 KiB of LDS on gfx950, which gives d_max <= 8191.
+constexpr size_t router_mlp_lds_bytes(int d_max) { return (size_t)(4 * d_max + 16 * 256 + 16 * 256) * sizeof(float); }
+constexpr size_t kRouterMlpStaticLds = 16;
+constexpr size_t kLdsPerWorkgroup = 160 * 1024;
+constexpr int kRouterMaxDmax = (int)((kLdsPerWorkgroup - kRouterMlpStaticLds - router_mlp_lds_bytes(0)) / (router_mlp_lds_bytes(1) - router_mlp_lds_bytes(0)));
+static_assert(router_mlp_lds_bytes(kRouterMaxDmax) + kRouterMlpStaticLds <= kLdsPerWorkgroup &&
+              router_mlp_lds_bytes(kRouterMaxDmax + 1) + kRouterMlpStaticLds > kLdsPerWorkgroup, "kRouterMaxDmax is the widest launchable d_max");
+static_assert(kRouterMaxDmax == 8191, "include/ragroute_hip.h states d_max <= 8191");
 constexpr int kRouterMfmaMinQueries = 32;   // batches from this size take the matrix-core form (needs a workspace)
 size_t router_workspace_bytes(const rr_router_weights* w, int nq);
 hipError_t launch_router_mlp_ws(const rr_router_weights* w, const float* xq, int nq, float* logits, uint8_t* mask, void* ws,

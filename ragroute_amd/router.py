@@ -81,7 +81,9 @@ class CorpusRoutingNN:
 
     def forward(self, x):
         """Logits [R,1] of raw feature rows x [R,input_dim] (float32 tensor or array), on the GPU kernel
-        with nothing folded (fc1 applied to the whole row)."""
+        with nothing folded (fc1 applied to the whole row).  The row is the kernel's d_max, so input_dim is at most 8191
+        (include/ragroute_hip.h): FeB4RAG's 8205-wide rows are refused (RR_ERR_INVALID) - they never ran: no kernel that serves one
+        source on one model fits them; the routing path folds them to d_max = 4096."""
         if self._plain is None:
             self._plain = FoldedRouter.plain(self._sd)
         xt = torch.as_tensor(np.asarray(x, dtype=np.float32) if not isinstance(x, torch.Tensor) else x).to("cuda", torch.float32)

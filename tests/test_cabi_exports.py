@@ -57,6 +57,25 @@ def test_argument_validation_without_gpu():
     assert L.rr_flat_search_workspace_bytes(0) == 0
 
 
+def test_router_header_widths_every_batch_size_can_serve():
+    """d_max is 1 ... 8191: the small-batch kernel holds 4 queries of d_max floats beside 32 KiB of partial sums in the 160 KiB of a
+    workgroup's LDS (rr::kRouterMaxDmax, derived from the expression launch_router_mlp sizes its LDS with).  8192 - which the
+    matrix-core form alone could serve - and 8448 are refused by every router entry point before any device call (the pointers
+    here are not device pointers, and no GPU is needed); 8191 passes the header check (nq = 0 needs no buffers)."""
+    from ragroute_amd import _lib
+    L, W = _lib.lib(), _lib.RouterWeightsStruct
+    for d_max, ok in ((8191, True), (8192, False), (8448, False), (1, True), (0, False)):
+        for n_sources, n_models, nq in ((4, 1, 1), (13, 8, 5), (13, 8, 256), (8, 1, 33)):
+            w = W(n_sources=n_sources, d_max=d_max, n_models=n_models, model_of_source=8, w1q=8, c1=8, ln1_g=8, ln1_b=8, w2=8, b2=8, ln2_g=8,
+                  ln2_b=8, w3=8, b3=0.0, prob_threshold=0.5, ln_eps=1e-5)
+            assert (L.rr_router_workspace_bytes(ctypes.byref(w), nq) > 0) == (ok and nq >= 32)
+            assert L.rr_router_mlp(ctypes.byref(w), None, 0, None, None, None) == (0 if ok else -1)
+            assert L.rr_router_mlp_ws(ctypes.byref(w), None, 0, None, None, None, 0, None) == (0 if ok else -1)
+            if not ok:
+                assert L.rr_router_mlp(ctypes.byref(w), 8, nq, 8, 8, None) == -1 and b"bad weight header" in L.rr_last_error()
+                assert L.rr_router_mlp_ws(ctypes.byref(w), 8, nq, 8, 8, 8, 1 << 40, None) == -1 and b"d_max" in L.rr_last_error()
+
+
 def test_segment_row_counts_cannot_overflow():
     from ragroute_amd import _lib
     L, S = _lib.lib(), _lib.SegmentStruct

@@ -99,6 +99,110 @@ def test_merge_compares_zeros_as_ieee_and_keeps_their_sign(gpu):
         assert Dg.cpu().numpy().tobytes() == Dr.tobytes()
 
 
+def _merge_both_ways(D, I, k):
+    """rr_merge_topk against the oracle, bit for bit, descending and ascending."""
+    from oracle import oracle as O
+    from ragroute_amd.rerank import merge_topk
+    for desc in (True, False):
+        Dg, Ig = merge_topk(torch.from_numpy(D).cuda(), torch.from_numpy(I).cuda(), k, desc)
+        Dr, Ir = O.merge_topk(D, I, k, desc)
+        assert np.array_equal(Ig.cpu().numpy(), Ir), (D.shape, k, desc)
+        assert Dg.cpu().numpy().tobytes() == Dr.tobytes(), (D.shape, k, desc)
+    return Dr, Ir
+
+
+@pytest.mark.parametrize("m", [8191, 8192])
+def test_merge_at_the_candidate_cap(gpu, m):
+    """m = 8192 fills the kernel's LDS arrays, m = 8191 is sorted as 8192 with one filler entry; ids up to 2^62 (bit 63 of the id
+    slot carries the sign of a zero score); the best candidate of either direction is the LAST one of its row."""
+    rng = np.random.default_rng(m)
+    D = np.round(rng.standard_normal((3, m)) * 64).astype(np.float32) / 4        # ties
+    I = np.stack([rng.permutation(4 * m)[:m] for _ in range(3)]).astype(np.int64)
+    I[1] += (1 << 62) - 4 * m
+    I[1, 17] = 1 << 62
+    I[2, ::3] = -1
+    D[0, m - 1], D[1, m - 1] = 1e6, -1e6
+    D[2, 4], D[2, 5] = 0.0, -0.0
+    for k in (1, 100, 1024):
+        Dr, Ir = _merge_both_ways(D, I, k)
+    assert Ir[1, 0] == I[1, m - 1] and Dr[1, 0] == -1e6 and I.max() == 1 << 62 and (Ir[1] >= (1 << 62) - 4 * m).all()
+
+
+def test_merge_refuses_more_than_8192_candidates(gpu):
+    from ragroute_amd._lib import lib
+    m, k = 8193, 4
+    D = torch.zeros((2, m), device=gpu)
+    I = torch.arange(2 * m, device=gpu).view(2, m)
+    Do = torch.full((2, k), 7.0, device=gpu)
+    Io = torch.full((2, k), 7, dtype=torch.int64, device=gpu)
+    assert lib().rr_merge_topk(D.data_ptr(), I.data_ptr(), 2, m, k, 1, Do.data_ptr(), Io.data_ptr(), None) == -2    # RR_ERR_UNSUPPORTED
+    torch.cuda.synchronize()
+    assert bool((Do == 7).all()) and bool((Io == 7).all())
+
+
+def test_merge_pads_when_k_exceeds_the_candidates(gpu):
+    """k > m, and k > the real candidates of a row: the tail is (-inf, -1) descending, (+inf, -1) ascending."""
+    for m, k in [(1, 3), (2, 5), (5, 9), (130, 200)]:
+        rng = np.random.default_rng(m)
+        D = rng.standard_normal((3, m)).astype(np.float32)
+        I = np.stack([rng.permutation(10 * m)[:m] for _ in range(3)]).astype(np.int64)
+        I[1, : (m + 1) // 2] = -1
+        I[2] = -1
+        Dr, Ir = _merge_both_ways(D, I, k)
+        assert (Ir[2] == -1).all() and (Dr[2] == np.inf).all() and (Ir[0, :m] >= 0).all() and (Ir[0, m:] == -1).all()
+
+
+def test_merge_infinite_scores_beside_padding(gpu):
+    """Real candidates scoring +inf and -inf beside (-inf, -1) and (+inf, -1) padding.  include/ragroute_hip.h: entries with id < 0
+    are padding and sort last - so a real -inf (descending) or +inf (ascending) candidate comes before every padding entry, by
+    ascending id among its equals.  The oracle says the same; the expected lists are written out, so the header decides."""
+    inf = np.inf
+    D = np.array([[inf, -inf, 1.0, -inf, inf, -inf, inf, -2.5]], np.float32)
+    I = np.array([[7, 3, 5, -1, -1, 2, 1, 9]], np.int64)
+    Dr, Ir = _merge_both_ways(D, I, 8)          # ascending, the last direction run
+    assert Ir.tolist() == [[2, 3, 9, 5, 1, 7, -1, -1]] and Dr.tolist() == [[-inf, -inf, -2.5, 1.0, inf, inf, inf, inf]]
+    from oracle import oracle as O
+    Dd, Id = O.merge_topk(D, I, 8, True)
+    assert Id.tolist() == [[1, 7, 5, 9, 2, 3, -1, -1]] and Dd.tolist() == [[inf, inf, 1.0, -2.5, -inf, -inf, -inf, -inf]]
+    for k in (3, 5, 6):                         # the cut falls inside the run of infinite real candidates
+        _merge_both_ways(D, I, k)
+
+
+def test_merge_gathered_at_the_candidate_cap(gpu):
+    """rr_merge_topk_gathered at n_ranks x slots x k_in = 8192, with -0.0 and +0.0 scores (equal for the merge, each keeps its sign)."""
+    from oracle import oracle as O
+    from ragroute_amd import sharded as S
+    rng = np.random.default_rng(8)
+    world, slots, B, k_in, k = 8, 4, 3, 256, 50
+    bufs = []
+    for r in range(world):
+        buf, D, I = S.alloc_packed(B, k_in, gpu, slots)
+        d = np.round(rng.standard_normal((slots, B, k_in)) * 2).astype(np.float32) / 2
+        d[d == 0] = np.where(rng.random(int((d == 0).sum())) < 0.5, np.float32(-0.0), np.float32(0.0))
+        D.copy_(torch.from_numpy(d))
+        I.copy_(torch.from_numpy(rng.permutation(slots * B * k_in).reshape(slots, B, k_in).astype(np.int64) + (r << 40)))
+        bufs.append(buf)
+    out = torch.stack(bufs)
+    assert world * slots * k_in == 8192
+    Dl, Il = S.unpack_gathered(out, B, k_in, slots)
+    assert np.signbit(Dl.cpu().numpy()[Dl.cpu().numpy() == 0]).any()
+    for desc in (True, False):
+        Dg, Ig = S.merge_gathered(out, B, k_in, slots, k, desc)
+        Dr, Ir = O.merge_topk(Dl.cpu().numpy(), Il.cpu().numpy(), k, desc)
+        assert np.array_equal(Ig.cpu().numpy(), Ir) and Dg.cpu().numpy().tobytes() == Dr.tobytes(), desc
+    # values are multiples of 1/2 in about [-4, 4]: the 50 best of 8192 do not reach the zeros - a row of zeros only does
+    for r in range(world):
+        out[r, : S.packed_layout(B, k_in, slots)[0]].view(torch.float32).view(slots, B, k_in)[:, 0, :].mul_(0.0)
+    Dl, Il = S.unpack_gathered(out, B, k_in, slots)
+    z = Dl.cpu().numpy()[0]
+    assert (z == 0).all() and np.signbit(z).any() and not np.signbit(z).all()
+    for desc in (True, False):
+        Dg, Ig = S.merge_gathered(out, B, k_in, slots, k, desc)
+        Dr, Ir = O.merge_topk(Dl.cpu().numpy(), Il.cpu().numpy(), k, desc)
+        assert np.array_equal(Ig.cpu().numpy(), Ir) and Dg.cpu().numpy().tobytes() == Dr.tobytes(), desc
+        assert np.signbit(Dr[0]).any()
+
+
 def test_merge_gathered_reads_the_exchange_buffer_in_place(gpu):
     """rr_merge_topk_gathered on a buffer laid out as the all-gather leaves it ([rank][D f32[slots][B][k] | pad | I i64[slots][B][k]])
     against the layout statement (sharded.unpack_gathered) + the oracle's merge; odd B*k*slots exercises the 8-byte pad."""
