@@ -70,6 +70,41 @@ int rr_rows_to_half(const float* d_x, int64_t n, int64_t d, int64_t ld_in, void*
  * (entries >= d are zero, matching the zero padding of router.py:150). */
 int rr_centroid(const void* d_xb, int dtype, int64_t n_rows, int dim, int d, float* d_out, void* stream);
 
+/* ---- Clustering a stored corpus into a federation (k-means) ------------------------------------------------------------------
+ * The reference's wikipedia federation is ONE DPR index cut into ten k-means clusters (`NUM_CLUSTERS = 10`,
+ * scripts/train/train_mmlu_router.py:26-30; faiss_index_{c}_normalized.index, ragroute/data_source.py:55-62; sources named by
+ * cluster number, ragroute/router.py:140-144); it only consumes those files, which were made off-tree.  These two entry points are
+ * the Lloyd iteration that makes them from a corpus already in the scan format (ragroute_amd/cluster.py drives them). */
+enum { RR_MAX_CLUSTERS = 64 };
+
+/* Nearest centroid of every stored row.  score(r, c) = x_r . c_c - bias[c], products of the STORED half values, f32
+ * accumulation (as rr_flat_search), one f32 subtraction (as the L2 scan's fl(fl(a.b) - h(b))).  bias NULL = 0: maximum inner
+ * product.  bias = rr_half_sqnorms of the centroid rows: the nearest centroid under squared L2, |x - c|^2 = |x|^2 - 2 score.
+ *   d_xb      device [n_rows][dim] f16/bf16, dim == rr_padded_dim(d), as rr_flat_search
+ *   d_cent    device [n_clusters][dim] same dtype, zero padded; 1 <= n_clusters <= RR_MAX_CLUSTERS
+ *   d_assign  device i32 [n_rows]: the c with the greatest non-NaN score, the LOWEST such c on ties; -1 when every score is NaN
+ *   d_score   optional device f32 [n_rows]: that score (NaN beside -1)
+ * Reads no row at or beyond n_rows, writes no entry at or beyond n_rows; n_rows == 0 is a no-op; n_rows <= 2^32 - 32.
+ * RR_ERR_INVALID: a null pointer (d_cent; d_xb / d_assign with rows to read), a bad dtype, n_clusters outside 1 .. 64, n_rows < 0;
+ * RR_ERR_UNSUPPORTED: dim != rr_padded_dim(d), n_rows > 2^32 - 32 - all before any device call. */
+int rr_cluster_assign(const void* d_xb, int dtype, int64_t n_rows, int dim, const void* d_cent, const float* d_bias,
+                      int n_clusters, int32_t* d_assign, float* d_score, void* stream);
+
+/* Means of the rows assigned to each cluster (the Lloyd update; also the router's per-source centroid of a federation).
+ *   d_assign     i32 [n_rows]; entries outside [0, n_clusters) are skipped
+ *   d_counts     device i64 [n_clusters]: members per cluster, exact
+ *   d_centroids  device f32 [n_clusters][d], IN/OUT: row c becomes the mean of its members' stored values (columns < d);
+ *                a cluster without members keeps the row it had
+ *   d_ws         device workspace of rr_cluster_workspace_bytes(n_rows, dim, n_clusters) bytes, 16-byte aligned
+ * Accuracy contract: |centroid[c][j] - mean64| <= (4098 * 2^-24 * sum_{r in c} |x_rj|) / count + one f32 rounding of the mean
+ * (no f32 addition chain longer than 4096 terms; wider accumulation above that).  Deterministic: the same arguments give the
+ * same bits on every call on one device (no float atomics - rr_centroid's last bits move between calls; these must not).
+ * RR_ERR_INVALID: a null pointer, a bad dtype, n_clusters outside 1 .. 64, d outside 1 .. dim, n_rows < 0, a misaligned workspace;
+ * RR_ERR_UNSUPPORTED: dim != rr_padded_dim(d), n_rows > 2^32 - 32; RR_ERR_WORKSPACE: a short workspace - all before any device call. */
+size_t rr_cluster_workspace_bytes(int64_t n_rows, int dim, int n_clusters);   /* 0 = invalid sizes */
+int rr_cluster_means(const void* d_xb, int dtype, int64_t n_rows, int dim, int d, const int32_t* d_assign, int n_clusters,
+                     float* d_centroids, int64_t* d_counts, void* d_ws, size_t ws_bytes, void* stream);
+
 /* Bytes of device workspace rr_flat_search (and _l2, _segments) needs for this k on the current device: for rows of any
  * width, or — smaller for dim <= 768 — for rows of one padded width. */
 size_t rr_flat_search_workspace_bytes(int k);

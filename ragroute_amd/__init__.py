@@ -7,6 +7,7 @@ Public surface (mirrors reference ragroute/{data_source,router,rerank}.py; see I
     rerank.rerank_medrag / rerank_feb4rag / rerank_wikipedia / merge_topk
     pipeline.RetrievalPipeline, sharded.*              device-side federation (one process per GPU)
     queue_manager.QueryQueue / QueryBatcher
+    cluster.kmeans / federate / route_nearest / cluster_stats / write_federation   one corpus into a routed federation
 """
 from ._lib import RagrouteHipError  # noqa: F401
 

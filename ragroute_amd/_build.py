@@ -13,7 +13,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 OBJ_DIR = os.path.join(CSRC, "build")
 LIB_PATH = os.path.join(PKG, "libragroute_hip.so")
-SOURCES = ["capi.hip", "flat_scan.hip", "flat_scan_wide.hip", "select.hip", "prep.hip", "router.hip", "screen.hip", "faithful.hip"]
+SOURCES = ["capi.hip", "flat_scan.hip", "flat_scan_wide.hip", "select.hip", "prep.hip", "router.hip", "screen.hip", "faithful.hip", "cluster.hip"]
 HEADERS = ["rr_common.h", "rr_kernels.h", "rr_sort.h", "flat_scan_common.h"]
 LLVM_BIN = os.environ.get("RR_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 

@@ -12,6 +12,7 @@ RR_MAX_K = 1024
 RR_QUERY_BLOCK = 256
 RR_MAX_SEGMENTS = 32
 RR_SEGMENT_ALIGN = 256
+RR_MAX_CLUSTERS = 64
 
 EXPORTS = ("rr_version", "rr_last_error", "rr_device_cus", "rr_padded_dim", "rr_l2_normalize_f32", "rr_rows_to_half",
            "rr_flat_search_workspace_bytes", "rr_flat_search", "rr_merge_topk", "rr_router_mlp", "rr_profile_begin",
@@ -20,7 +21,8 @@ EXPORTS = ("rr_version", "rr_last_error", "rr_device_cus", "rr_padded_dim", "rr_
            "rr_build_flags", "rr_merge_topk_gathered", "rr_flat_scan_kernel_name", "rr_flat_search_segments", "rr_flat_search_workspace_bytes_for",
            "rr_faithful_build", "rr_flat_search_faithful_workspace_bytes", "rr_flat_search_faithful",
            "rr_flat_search_f32_exact_workspace_bytes", "rr_flat_search_f32_exact", "rr_flat_search_segments_l2",
-           "rr_flat_search_faithful_l2_workspace_bytes", "rr_flat_search_faithful_l2", "rr_flat_search_f32_exact_l2")
+           "rr_flat_search_faithful_l2_workspace_bytes", "rr_flat_search_faithful_l2", "rr_flat_search_f32_exact_l2",
+           "rr_cluster_assign", "rr_cluster_workspace_bytes", "rr_cluster_means")
 
 
 class RouterWeightsStruct(ctypes.Structure):
@@ -102,6 +104,10 @@ def lib():
         L.rr_flat_search_faithful_l2.argtypes = [vp, vp, i32, vp, i64, vp, i64, i32, i32, ctypes.POINTER(SegmentStruct), i32, vp, vp, i32,
                                                  i32, i32, vp, vp, vp, vp, vp, sz, vp, i64, vp]
         L.rr_flat_search_f32_exact_l2.argtypes = L.rr_flat_search_f32_exact.argtypes
+        L.rr_cluster_assign.argtypes = [vp, i32, i64, i32, vp, vp, i32, vp, vp, vp]
+        L.rr_cluster_workspace_bytes.argtypes = [i64, i32, i32]
+        L.rr_cluster_workspace_bytes.restype = sz
+        L.rr_cluster_means.argtypes = [vp, i32, i64, i32, i32, vp, i32, vp, vp, vp, sz, vp]
         L.rr_profile_begin.argtypes = [i32]
         L.rr_profile_end.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
         _LIB = L

@@ -310,7 +310,7 @@ const char kBuildFlags[] = "unknown (not built by ragroute_amd/_build.py)";
 
 extern "C" {
 
-int rr_version(void) { return 800; }  // 0.8.0: f32-faithful exact search under the squared-L2 metric (rr_flat_search_faithful_l2, rr_flat_search_f32_exact_l2); 0.7.0: segmented squared-L2 search (rr_flat_search_segments_l2); 0.6.0: f32-faithful exact search (rr_flat_search_faithful, rr_flat_search_f32_exact); 0.5.0: row-split wide-row kernel for L2 / any k / 193+ queries (8 candidate buffers per workgroup on wide rows at every k: larger workspace), tuning variables ignored by product builds, cursor-free plain scans
+int rr_version(void) { return 900; }  // 0.9.0: k-means over a stored corpus (rr_cluster_assign, rr_cluster_means, rr_cluster_workspace_bytes); 0.8.0: f32-faithful exact search under the squared-L2 metric (rr_flat_search_faithful_l2, rr_flat_search_f32_exact_l2); 0.7.0: segmented squared-L2 search (rr_flat_search_segments_l2); 0.6.0: f32-faithful exact search (rr_flat_search_faithful, rr_flat_search_f32_exact); 0.5.0: row-split wide-row kernel for L2 / any k / 193+ queries (8 candidate buffers per workgroup on wide rows at every k: larger workspace), tuning variables ignored by product builds, cursor-free plain scans
 const char* rr_build_flags(void) { return kBuildFlags; }
 const char* rr_last_error(void) { return g_err; }
 int rr_device_cus(void) {
@@ -341,6 +341,46 @@ int rr_centroid(const void* xb, int dtype, int64_t n_rows, int dim, int d, float
     return fail(RR_ERR_INVALID, "rr_centroid: bad arguments%s");
   if (!rr::half_dtype(dtype)) return fail(RR_ERR_INVALID, "rr_centroid: bad dtype%s");
   return hip_status(rr::launch_centroid(xb, dtype, n_rows, dim, d, out, (hipStream_t)stream), "rr_centroid");
+}
+
+static bool cluster_sizes_ok(int64_t n_rows, int dim, int n_clusters) {
+  return n_rows >= 0 && n_rows <= 0xFFFFFFE0ll && n_clusters >= 1 && n_clusters <= RR_MAX_CLUSTERS && dim > 0 && rr::scan_padded_dim(dim) == dim;
+}
+
+int rr_cluster_assign(const void* xb, int dtype, int64_t n_rows, int dim, const void* cent, const float* bias, int n_clusters,
+                      int32_t* assign, float* score, void* stream) {
+  if (n_rows < 0) return fail(RR_ERR_INVALID, "rr_cluster_assign: negative row count%s");
+  if (n_clusters < 1 || n_clusters > RR_MAX_CLUSTERS) return fail(RR_ERR_INVALID, "rr_cluster_assign: n_clusters must be in [1, 64]%s");
+  if (!rr::half_dtype(dtype)) return fail(RR_ERR_INVALID, "rr_cluster_assign: bad dtype%s");
+  if (!cent || ((!xb || !assign) && n_rows > 0)) return fail(RR_ERR_INVALID, "rr_cluster_assign: null pointer%s");
+  if (dim <= 0 || rr::scan_padded_dim(dim) != dim) return fail(RR_ERR_UNSUPPORTED, "rr_cluster_assign: dim must equal rr_padded_dim(d)%s");
+  if (n_rows > 0xFFFFFFE0ll) return fail(RR_ERR_UNSUPPORTED, "rr_cluster_assign: more than 2^32-32 rows%s");
+  if (n_rows == 0) return RR_OK;
+  const int cus = device_cus();
+  if (cus <= 0) return fail(RR_ERR_HIP, "rr_cluster_assign: no HIP device%s");
+  return hip_status(rr::launch_cluster_assign(xb, dtype, n_rows, dim, cent, bias, n_clusters, assign, score, cus, (hipStream_t)stream),
+                    "rr_cluster_assign");
+}
+
+size_t rr_cluster_workspace_bytes(int64_t n_rows, int dim, int n_clusters) {
+  if (!cluster_sizes_ok(n_rows, dim, n_clusters)) return 0;
+  return rr::cluster_means_plan(n_rows, dim, n_clusters).total_bytes;
+}
+
+int rr_cluster_means(const void* xb, int dtype, int64_t n_rows, int dim, int d, const int32_t* assign, int n_clusters, float* centroids,
+                     int64_t* counts, void* ws, size_t ws_bytes, void* stream) {
+  if (n_rows < 0) return fail(RR_ERR_INVALID, "rr_cluster_means: negative row count%s");
+  if (n_clusters < 1 || n_clusters > RR_MAX_CLUSTERS) return fail(RR_ERR_INVALID, "rr_cluster_means: n_clusters must be in [1, 64]%s");
+  if (!rr::half_dtype(dtype)) return fail(RR_ERR_INVALID, "rr_cluster_means: bad dtype%s");
+  if (d < 1 || d > dim) return fail(RR_ERR_INVALID, "rr_cluster_means: d must be in [1, dim]%s");
+  if (!centroids || !counts || !ws || ((!xb || !assign) && n_rows > 0)) return fail(RR_ERR_INVALID, "rr_cluster_means: null pointer%s");
+  if ((uintptr_t)ws % 16 != 0) return fail(RR_ERR_INVALID, "rr_cluster_means: the workspace must be 16-byte aligned%s");
+  if (rr::scan_padded_dim(dim) != dim) return fail(RR_ERR_UNSUPPORTED, "rr_cluster_means: dim must equal rr_padded_dim(d)%s");
+  if (n_rows > 0xFFFFFFE0ll) return fail(RR_ERR_UNSUPPORTED, "rr_cluster_means: more than 2^32-32 rows%s");
+  if (ws_bytes < rr::cluster_means_plan(n_rows, dim, n_clusters).total_bytes)
+    return fail(RR_ERR_WORKSPACE, "rr_cluster_means: workspace smaller than rr_cluster_workspace_bytes%s");
+  return hip_status(rr::launch_cluster_means(xb, dtype, n_rows, dim, d, assign, n_clusters, centroids, counts, ws, (hipStream_t)stream),
+                    "rr_cluster_means");
 }
 
 size_t rr_flat_search_workspace_bytes(int k) { return rr_flat_search_workspace_bytes_for(k, rr::kMaxDim); }   // any dim

@@ -111,6 +111,17 @@ hipError_t launch_rows_to_half(const float* x, int64_t n, int64_t d, int64_t ld_
 hipError_t launch_half_sqnorms(const void* xb, int dtype, int64_t n, int dim, float* out, hipStream_t st);
 hipError_t launch_centroid(const void* xb, int dtype, int64_t n, int dim, int d, float* out, hipStream_t st);
 
+// cluster.hip (k-means over a stored corpus: nearest-centroid assignment, per-cluster means)
+// cus: compute units of the current device (sizes the persistent assignment grid; results do not depend on it)
+hipError_t launch_cluster_assign(const void* xb, int dtype, int64_t n, int dim, const void* cent, const float* bias, int C,
+                                 int32_t* assign, float* score, int cus, hipStream_t st);
+// How rr_cluster_means cuts the corpus: `ranges` runs of rows_per_range rows, each walked in order by `slabs` workgroups of `threads`
+// threads (two columns per thread); the workspace holds every range's f64 sums [ranges][C][dim], then its i64 counts [ranges][C].
+struct ClusterMeansPlan { int threads, slabs, ranges; int64_t rows_per_range; size_t sums_bytes, total_bytes; };
+ClusterMeansPlan cluster_means_plan(int64_t n, int dim, int C);
+hipError_t launch_cluster_means(const void* xb, int dtype, int64_t n, int dim, int d, const int32_t* assign, int C, float* centroids,
+                                int64_t* counts, void* ws, hipStream_t st);
+
 // screen.hip (int8 screening copy + exact re-scoring)
 hipError_t launch_screen_build(const void* xb, int dtype, int64_t n, int dim, int8_t* x8, int dim8, uint32_t* stats, hipStream_t st);
 hipError_t launch_screen_queries(const void* xq, int dtype, int nq, int dim, int8_t* q8, int dim8, const uint32_t* stats, float* qinfo,
